@@ -16,6 +16,14 @@ is that process; the other ranks only join the barriers (gloo, on the CPU).
 --process-per-gpu keeps the earlier harness instead (one process per GPU,
 torch.distributed over RCCL).
 
+A plain run (python bench.py --gpus N --steps K --warmup W) sets up, warms
+up, times the K steps and prints the headline line with its roofline (which
+is derived from the timed region itself and from committed PMC summaries, no
+run of its own). --dump-outputs DIR writes what the last timed step computed
+(each device's verdicts, one float32 0/1 per signature) as DIR/<name>.npy;
+the inputs are deterministic, so two builds compare output for output.
+Everything below except `roofline` is measured only with --full.
+
 Extra fields on the JSON line:
   roofline       -- VALU integer-MAC roofline of the verify kernel: algorithmic
                     work = 300,000 32x32->64 MACs per verification
@@ -48,7 +56,7 @@ Extra fields on the JSON line:
                     signatures checked exactly; own roofline; the radix-2^16 key
                     combs and the generic kernel beside it
   sr25519        -- configs[4]: 10k sr25519 verifications per step (N=1 only)
-Run: python bench.py [--gpus N --steps K --warmup W]
+Run: python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
 """
 from __future__ import annotations
 
@@ -93,6 +101,11 @@ def parse():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--n", type=int, default=10_000, help="signatures per GPU per step")
     ap.add_argument("--mode", choices=["go", "zip215"], default="go")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure the side lines (other mode, host-API paths, CPU baselines, latencies, "
+                         "replays, sr25519); the --no-* options below prune them")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the verdicts of the last timed step as DIR/verdicts_dev<g>.npy (float32)")
     ap.add_argument("--cpu-seconds", type=float, default=20.0, help="CPU-seconds of oracle work for cpu_baseline")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--latency-iters", type=int, default=1000)
@@ -300,6 +313,22 @@ class Devices:
             full[-1] = mask[-1] = np.uint64((1 << (self.n % 64)) - 1)
         return all(np.array_equal(self.t[g]["bm"].cpu().numpy().view(np.uint64) & mask, full)
                    for g in range(self.n_dev))
+
+    def dump(self, out_dir, first=0):
+        """What the step's caller receives, as DIR/verdicts_dev<g>.npy: each
+        device's verdict bitmap unpacked to one float32 per signature (1.0 =
+        accepted; the unspecified bits past n are left out). At most 64 MB in
+        all: beyond that a fixed sample (seed 0, ascending indices) of each
+        device's verdicts."""
+        from cometbft_amd.parallel import unpack_bitmap
+
+        os.makedirs(out_dir, exist_ok=True)
+        cap = (60 << 20) // (4 * self.n_dev)
+        pick = np.sort(np.random.default_rng(0).choice(self.n, cap, replace=False)) if self.n > cap else None
+        for g in range(self.n_dev):
+            v = unpack_bitmap(self.t[g]["bm"].cpu().numpy().view(np.uint64), self.n)
+            np.save(os.path.join(out_dir, f"verdicts_dev{first + g}.npy"),
+                    (v if pick is None else v[pick]).astype(np.float32))
 
 
 # The GPU leaves its idle clock state only after some milliseconds of load: the
@@ -1207,6 +1236,8 @@ def process_per_gpu_main(args):
 
     barrier = (lambda: dist.barrier()) if world > 1 else (lambda: None)
     elapsed, kms = timed_steps(ctx, step, args.steps, args.warmup, barrier)
+    if args.dump_outputs:
+        D.dump(args.dump_outputs, first=rank)
     if world > 1:
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -1277,6 +1308,8 @@ def main():
     elapsed, kernel_ms = timed_steps(ctx, lambda: D.step(ctx, mode), args.steps, args.warmup, barrier)
     run_head = dict(LAST_RUN)
     ok = D.verdicts_ok()
+    if args.dump_outputs:
+        D.dump(args.dump_outputs)
     elapsed = max_over_ranks(elapsed)
     total = n_dev * args.n * args.steps
     value = total / elapsed
@@ -1319,75 +1352,76 @@ def main():
                                "(back-to-back launches): region / steps; the library's sampled per-call "
                                "events are config.devices.sampled_kernel_ms"},
     }
-    # ZIP-215 mode on the same inputs (the north-star semantics)
-    el_z, kms_z = timed_steps(ctx, lambda: D.step(ctx, 1 - mode), args.steps, 2, lambda: None)
-    line["zip215" if mode == 0 else "go_stdlib"] = {
-        "value": round(n_dev * args.n * args.steps / el_z, 1), "unit": "verifs/s",
-        "ms_per_step": round(el_z / args.steps * 1e3, 4), "kernel_ms": round(kms_z, 4),
-        "frac": round(args.n * MACS_PER_VERIFY / (kms_z * 1e-3) / 1e12 / INT_MAC_PEAK_T, 4)}
-    # the side lines below never cost the headline: a failure (say, a
-    # collective that a multi-GPU node refuses) is recorded in its own key
-    def aux(key, fn):
-        try:
-            line[key] = fn()
-        except Exception as e:  # noqa: BLE001 -- reported in the line, not swallowed
-            line[key] = {"error": f"{type(e).__name__}: {e}"[:400]}
-            print(f"bench: {key} failed: {e!r}", file=sys.stderr, flush=True)
-
-    aux("e2e_10k", lambda: e2e_10k(Context(device=0), D.host[0], mode))
-    if not args.no_latency and n_dev == 1:
-        aux("verify_commit_10k",
-            lambda: verify_commit_10k(Context(device=0), mode, 200, line["e2e_10k"].get("ms") or 0.0))
-    if n_dev == 1 and not args.no_keyset:
-        aux("keyset_10k", lambda: keyset_10k(ctx, D, mode, args.steps))
-    if not args.no_cpu_baseline and n_dev == 1:  # rank 0 at N=1 only (bench contract)
-        pk, sigs, m, off = D.host[0]
-        line["cpu_baseline"] = cpu_baseline(pk, sigs, m, off, mode, args.cpu_seconds)
-        cb = line["cpu_baseline"]
-        z = line.get("zip215") or line.get("go_stdlib")
-        cb["gpu_over_cpu"] = round(value / n_dev / cb["value"], 1)
-        cb["single_core"]["gpu_over_cpu"] = round(value / n_dev / cb["single_core"]["value"], 1)
-        cb["quota_bound_all_threads"]["gpu_over_cpu"] = round(value / n_dev / cb["quota_bound_all_threads"]["value"],
-                                                              1)
-        ex = cb["extrapolated_all_cores"]
-        if ex["value"]:
-            ex["gpu_over_cpu"] = round(value / n_dev / ex["value"], 1)
-            ex["gpu_over_cpu_other_mode"] = round(z["value"] / n_dev / ex["value_other_mode"], 1)
-        try:
-            cb["crossover"] = crossover(Context(device=0), mode)
-        except Exception as e:  # noqa: BLE001 -- an aux figure never sinks the bench line
-            cb["crossover"] = {"error": f"{type(e).__name__}: {e}"[:400]}
-    if not args.no_latency and n_dev == 1:
-        aux("verify_commit_10k_keyset", lambda: verify_commit_10k_keyset(mode, 200))
-    if not args.no_latency:
-        aux("latency_150", lambda: latency_150(ctx, mode, args.latency_iters))
-        if n_dev == 1:
-            aux("latency_150_under_load", lambda: latency_150_under_load(mode, args.latency_iters))
-        if n_dev == 1:
-            aux("replay_150", lambda: replay_line(0))
-    if not args.no_light and n_dev == 1:
-        aux("light_client", lambda: light_line(0))
-    if not args.no_sr25519 and n_dev == 1:
-        aux("sr25519", lambda: sr25519_line(ctx, torch.device("cuda", 0), 10_000, 20, args.cpu_seconds / 4,
-                                            not args.no_cpu_baseline))
-    if not args.no_c3_host:
-        def c3h():
-            hctx = Context(devices=ordinals)
-            hctx.keyset_cache(4)  # a node registers its validator set once
-            pctx = Context(devices=ordinals)
-            pctx.keyset_cache(4)
-            try:
-                return c3_host_line(hctx, mode, n_heights=args.c3_heights, packed_ctx=pctx)
-            finally:
-                pctx.close()
-                hctx.close()
-        aux("replay_c3_host", c3h)
     c3 = None
-    if not args.no_c3:
-        del D
-        torch.cuda.empty_cache()
-        aux("replay_c3", lambda: c3_line(ctx, n_dev, mode, n_heights=args.c3_heights))
-        c3 = line["replay_c3"]
+    if args.full:
+        # ZIP-215 mode on the same inputs (the north-star semantics)
+        el_z, kms_z = timed_steps(ctx, lambda: D.step(ctx, 1 - mode), args.steps, 2, lambda: None)
+        line["zip215" if mode == 0 else "go_stdlib"] = {
+            "value": round(n_dev * args.n * args.steps / el_z, 1), "unit": "verifs/s",
+            "ms_per_step": round(el_z / args.steps * 1e3, 4), "kernel_ms": round(kms_z, 4),
+            "frac": round(args.n * MACS_PER_VERIFY / (kms_z * 1e-3) / 1e12 / INT_MAC_PEAK_T, 4)}
+        # the side lines below never cost the headline: a failure (say, a
+        # collective that a multi-GPU node refuses) is recorded in its own key
+        def aux(key, fn):
+            try:
+                line[key] = fn()
+            except Exception as e:  # noqa: BLE001 -- reported in the line, not swallowed
+                line[key] = {"error": f"{type(e).__name__}: {e}"[:400]}
+                print(f"bench: {key} failed: {e!r}", file=sys.stderr, flush=True)
+
+        aux("e2e_10k", lambda: e2e_10k(Context(device=0), D.host[0], mode))
+        if not args.no_latency and n_dev == 1:
+            aux("verify_commit_10k",
+                lambda: verify_commit_10k(Context(device=0), mode, 200, line["e2e_10k"].get("ms") or 0.0))
+        if n_dev == 1 and not args.no_keyset:
+            aux("keyset_10k", lambda: keyset_10k(ctx, D, mode, args.steps))
+        if not args.no_cpu_baseline and n_dev == 1:  # rank 0 at N=1 only (bench contract)
+            pk, sigs, m, off = D.host[0]
+            line["cpu_baseline"] = cpu_baseline(pk, sigs, m, off, mode, args.cpu_seconds)
+            cb = line["cpu_baseline"]
+            z = line.get("zip215") or line.get("go_stdlib")
+            cb["gpu_over_cpu"] = round(value / n_dev / cb["value"], 1)
+            cb["single_core"]["gpu_over_cpu"] = round(value / n_dev / cb["single_core"]["value"], 1)
+            qb = cb["quota_bound_all_threads"]
+            qb["gpu_over_cpu"] = round(value / n_dev / qb["value"], 1)
+            ex = cb["extrapolated_all_cores"]
+            if ex["value"]:
+                ex["gpu_over_cpu"] = round(value / n_dev / ex["value"], 1)
+                ex["gpu_over_cpu_other_mode"] = round(z["value"] / n_dev / ex["value_other_mode"], 1)
+            try:
+                cb["crossover"] = crossover(Context(device=0), mode)
+            except Exception as e:  # noqa: BLE001 -- an aux figure never sinks the bench line
+                cb["crossover"] = {"error": f"{type(e).__name__}: {e}"[:400]}
+        if not args.no_latency and n_dev == 1:
+            aux("verify_commit_10k_keyset", lambda: verify_commit_10k_keyset(mode, 200))
+        if not args.no_latency:
+            aux("latency_150", lambda: latency_150(ctx, mode, args.latency_iters))
+            if n_dev == 1:
+                aux("latency_150_under_load", lambda: latency_150_under_load(mode, args.latency_iters))
+            if n_dev == 1:
+                aux("replay_150", lambda: replay_line(0))
+        if not args.no_light and n_dev == 1:
+            aux("light_client", lambda: light_line(0))
+        if not args.no_sr25519 and n_dev == 1:
+            aux("sr25519", lambda: sr25519_line(ctx, torch.device("cuda", 0), 10_000, 20, args.cpu_seconds / 4,
+                                                not args.no_cpu_baseline))
+        if not args.no_c3_host:
+            def c3h():
+                hctx = Context(devices=ordinals)
+                hctx.keyset_cache(4)  # a node registers its validator set once
+                pctx = Context(devices=ordinals)
+                pctx.keyset_cache(4)
+                try:
+                    return c3_host_line(hctx, mode, n_heights=args.c3_heights, packed_ctx=pctx)
+                finally:
+                    pctx.close()
+                    hctx.close()
+            aux("replay_c3_host", c3h)
+        if not args.no_c3:
+            del D
+            torch.cuda.empty_cache()
+            aux("replay_c3", lambda: c3_line(ctx, n_dev, mode, n_heights=args.c3_heights))
+            c3 = line["replay_c3"]
     print(json.dumps(line), flush=True)
     barrier()
     if world > 1:

@@ -15,7 +15,7 @@ step() {  # step <name> <seconds> <cmd...>
   tail -3 "$OUT/$name.log"
   if [ $rc -ne 0 ]; then echo "!! $name failed rc=$rc"; tail -40 "$OUT/$name.log"; exit $rc; fi
 }
-QUICK="--no-cpu-baseline --no-latency --no-sr25519 --no-light --no-c3 --steps 20 --warmup 3"
+QUICK="--full --no-cpu-baseline --no-latency --no-sr25519 --no-light --no-c3 --steps 20 --warmup 3"
 step phases 120 ./tools/dbg/quad_debug
 step stats 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/stats" -o run -- python3 bench.py $QUICK
 step pmc_fetch 90 timeout -s KILL 80 rocprofv3 --pmc FETCH_SIZE --output-format csv -d "$OUT/pmc_fetch" -o run -- python3 bench.py $QUICK

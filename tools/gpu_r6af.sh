@@ -9,7 +9,7 @@ timeout -k 10 600 python -u -m pytest -x -v --timeout 120 --timeout-method threa
 tail -1 "$OUT/tests.txt"
 for R in 1 2; do
   for P in 1 0; do
-    CMTV_PREP_STREAM=$P timeout -k 10 400 python -u bench.py --no-cpu-baseline --no-latency --no-sr25519 --no-light --no-keyset --no-c3 --steps 5 > "$OUT/b_${P}_$R.json" 2> "$OUT/b_${P}_$R.err" || { tail "$OUT/b_${P}_$R.err"; exit 1; }
+    CMTV_PREP_STREAM=$P timeout -k 10 400 python -u bench.py --full --no-cpu-baseline --no-latency --no-sr25519 --no-light --no-keyset --no-c3 --steps 5 > "$OUT/b_${P}_$R.json" 2> "$OUT/b_${P}_$R.err" || { tail "$OUT/b_${P}_$R.err"; exit 1; }
     python3 -c "import json;d=json.loads(open('$OUT/b_${P}_$R.json').read().strip().splitlines()[-1]);h=d['replay_c3_host'];print('prep $P round $R', h['verify_commit']['ms_per_pass'], h['verify_commit']['value'], h['verify_commit_light']['ms_per_pass'], h['packed']['verify_commit']['ms_per_pass'])"
   done
 done

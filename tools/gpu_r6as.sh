@@ -12,6 +12,6 @@ for R in 1 2; do
   python3 -c "import json;L=open('$OUT/lat_$R.json').read().strip().splitlines();k=json.loads(L[0])['verify_commit_10k_keyset'];d=json.loads(L[-1])['latency_150_under_load'];print('lat $R keyset', k['p50_ms'], k['pinned']['p50_ms'], 'load', d['idle_p99_ms'], d['p50_ms'], d['p99_ms'], d['p99_over_idle_p99'])"
 done
 for P in 1 0; do
-  CMTV_PREP_STREAM=$P timeout -k 10 400 python -u bench.py --no-cpu-baseline --no-latency --no-sr25519 --no-light --no-keyset --no-c3 --steps 5 > "$OUT/b_$P.json" 2> "$OUT/b_$P.err" || { tail "$OUT/b_$P.err"; exit 1; }
+  CMTV_PREP_STREAM=$P timeout -k 10 400 python -u bench.py --full --no-cpu-baseline --no-latency --no-sr25519 --no-light --no-keyset --no-c3 --steps 5 > "$OUT/b_$P.json" 2> "$OUT/b_$P.err" || { tail "$OUT/b_$P.err"; exit 1; }
   python3 -c "import json;d=json.loads(open('$OUT/b_$P.json').read().strip().splitlines()[-1]);h=d['replay_c3_host'];print('c3h prep $P', h['verify_commit']['ms_per_pass'], h['verify_commit']['value'], h['verify_commit_light']['ms_per_pass'], h['packed']['verify_commit']['ms_per_pass'])"
 done

@@ -8,7 +8,7 @@ timeout -k 10 1000 python -u -m pytest tests -x -v -m gpu --timeout 300 --timeou
 rc=$?
 tail -5 "$OUT/pytest.log"
 [ $rc -eq 0 ] || exit $rc
-timeout -k 10 600 python -u bench.py --no-cpu-baseline --no-sr25519 --no-light --no-c3 --steps 20 > "$OUT/bench.json" 2> "$OUT/bench.err"
+timeout -k 10 600 python -u bench.py --full --no-cpu-baseline --no-sr25519 --no-light --no-c3 --steps 20 > "$OUT/bench.json" 2> "$OUT/bench.err"
 rc=$?
 tail -c 3000 "$OUT/bench.json"
 [ $rc -eq 0 ] || exit $rc

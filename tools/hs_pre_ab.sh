@@ -7,7 +7,7 @@ set -o pipefail
 OUT=gpurun_out/hs_pre_ab.txt
 : > "$OUT"
 for v in ${VALUES:-6 4 3 2 6}; do
-  CMTV_HS_PRE=$v timeout -k 10 200 python bench.py --steps 30 --no-c3 --no-light --no-keyset --no-latency \
+  CMTV_HS_PRE=$v timeout -k 10 200 python bench.py --full --steps 30 --no-c3 --no-light --no-keyset --no-latency \
     --no-cpu-baseline --no-sr25519 > gpurun_out/hs_pre_$v.json 2> gpurun_out/hs_pre_$v.err || exit 1
   CMTV_HS_PRE=$v timeout -k 10 200 python tools/vc10k_ab.py > gpurun_out/hs_pre_vc_$v.json 2>> gpurun_out/hs_pre_$v.err || exit 1
   python3 - "$v" >> "$OUT" <<'PY' || exit 1

@@ -5,7 +5,7 @@
 set -o pipefail
 rm -f gpurun_out/srpre.txt
 for v in 0 1 2 0 1 2; do
-  CMTV_HS_PRE=$v timeout -k 10 200 python bench.py --steps 20 --no-c3 --no-light --no-keyset --no-latency \
+  CMTV_HS_PRE=$v timeout -k 10 200 python bench.py --full --steps 20 --no-c3 --no-light --no-keyset --no-latency \
     --no-cpu-baseline > gpurun_out/srpre_$v.json 2>/dev/null || exit 1
   python3 -c "
 import json
