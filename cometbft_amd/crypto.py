@@ -304,9 +304,12 @@ class KeySet:
         return N.lib().cmtv_keyset_len(self._h)
 
     def free(self):
-        if self._h:
+        # cmtv_keyset_free reads the key set's context (its devices and streams):
+        # after the context was closed -- explicitly, or first in a garbage
+        # collection of a cycle holding both -- the handle is only dropped
+        if self._h and self.ctx.handle:
             N.lib().cmtv_keyset_free(self._h)
-            self._h = None
+        self._h = None
 
     def __del__(self):
         try:

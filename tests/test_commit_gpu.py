@@ -400,12 +400,14 @@ def test_speculative_verify_commit_matches(pinned):
     pk_buf = keep_v[0]  # the set's key bytes, rewritten in place below
 
     def outcome(c, commit, height, kind):
-        arena = T._Arena(c.alloc_pinned(4096 + 100 * (n + 1))) if pinned else None
-        cm, keep_c = T._pack_commit(commit, arena)
+        block = c.alloc_pinned(4096 + 100 * (n + 1)) if pinned else None
+        cm, keep_c = T._pack_commit(commit, T._Arena(block) if pinned else None)
         res = N.cmtv_commit_result()
         rc = N.lib().cmtv_verify_commit(c.handle, kind, 0, cid, len(cid), ctypes.byref(vs), ctypes.byref(b), height,
                                         ctypes.byref(cm), 0, 0, ctypes.byref(res), None, 0)
-        del keep_c
+        del cm, keep_c
+        if block is not None:
+            block.free()
         return rc, res.code, res.sig_index
 
     clean, _, _ = TU.make_commit(ctxs[0], sv, height=h)
@@ -423,7 +425,17 @@ def test_speculative_verify_commit_matches(pinned):
         got = [[outcome(c, cm, hh, kind) for cm, hh in cases] for c in ctxs]
         assert got[0] == got[1], (kind, got)
         assert got[0][0][0] == N.CMTV_OK and got[0][5][1] == N.COMMIT_ERR_HEIGHT
-    assert got[1][2][2] == -1 or True  # light may stop before #3001
+        if kind == N.VERIFY_COMMIT_LIGHT:
+            # the light check stops at the first signature with which the tallied
+            # power exceeds 2/3 of the total: the flipped #3001 counts only before it
+            powers = [v.voting_power for v in sv.valset.validators]
+            tallies = np.cumsum(powers)
+            reach = int(np.argmax(tallies > sum(powers) * 2 // 3)) + 1  # signatures the light check examines
+            for g in got:
+                if 3001 < reach:
+                    assert g[2][0] != N.CMTV_OK and g[2][1:] == (N.COMMIT_ERR_WRONG_SIGNATURE, 3001), g[2]
+                else:
+                    assert g[2] == (N.CMTV_OK, 0, -1), g[2]
     # the key array rewritten in place: key 11 now another validator's
     saved = pk_buf[32 * 11:32 * 12].copy()
     pk_buf[32 * 11:32 * 12] = pk_buf[32 * 12:32 * 13]

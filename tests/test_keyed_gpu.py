@@ -146,6 +146,26 @@ def test_keyset_belongs_to_its_context(gpu_ctx, gpu_ctx_lane):
     ks.free()
 
 
+def test_keyset_outlives_its_context():
+    """A key set dropped after its context was closed (what a garbage
+    collection of a cycle holding both can do, the context's __del__ first)
+    only forgets its handle: cmtv_keyset_free would read the closed context."""
+    import torch
+
+    if not torch.cuda.is_available():
+        pytest.skip("no GPU")
+    from cometbft_amd import Context
+
+    ctx = Context(device=0)
+    pk, _, _, _, _, _ = _valset_commits(2, 3, 5)
+    ks = ctx.register_keys(pk)
+    assert len(ks) == 2
+    ctx.close()
+    ks.free()
+    assert not ks.handle
+    ks.free()
+
+
 @pytest.mark.parametrize("wide", [False, True])
 @pytest.mark.parametrize("n", [530_000, 1_100_003])
 def test_keyed_batch_inversion(gpu_ctx_lane, corpus, n, wide):
