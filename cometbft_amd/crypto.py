@@ -13,18 +13,21 @@ Every verdict is computed on the GPU. There is no CPU fallback in this package.
 from __future__ import annotations
 
 import ctypes
+import hashlib
 import threading
 from typing import Sequence
 
 import numpy as np
 
 from . import _native as N
+from .ripemd160 import ripemd160
 
 MODE_GO_STDLIB = N.MODE_GO_STDLIB
 MODE_ZIP215 = N.MODE_ZIP215
 
 PUBKEY_SIZE = 32     # crypto/ed25519/ed25519.go:24
 SIGNATURE_SIZE = 64  # crypto/ed25519/ed25519.go:28
+SECP256K1_PUBKEY_SIZE = 33  # crypto/secp256k1/secp256k1.go:146
 
 
 def _u8(a: np.ndarray):
@@ -215,6 +218,39 @@ class Context:
         rc = N.lib().cmtv_verify_sr25519_device(self._h, n, d_pk, d_sig, d_msg, d_off, d_valid or None,
                                                 d_bitmap or None, ctypes.c_void_p(stream) if stream else None)
         N.check(rc, "cmtv_verify_sr25519_device")
+
+    # -------------------------------------------------------------- secp256k1
+    def verify_secp256k1(self, pk: np.ndarray, sig: np.ndarray, msg: np.ndarray, msg_off: np.ndarray,
+                         bitmap: bool = False):
+        """secp256k1 ECDSA verdicts (crypto/secp256k1/secp256k1.go:192-217) for
+        n 33-byte compressed keys and 64-byte r || s signatures in host arrays;
+        messages laid out as verify()."""
+        pk = np.ascontiguousarray(pk, dtype=np.uint8).reshape(-1, SECP256K1_PUBKEY_SIZE)
+        sig = np.ascontiguousarray(sig, dtype=np.uint8).reshape(-1, 64)
+        n = pk.shape[0]
+        if sig.shape[0] != n or len(msg_off) != n + 1:
+            raise ValueError("pk / sig / msg_off sizes disagree")
+        msg = np.ascontiguousarray(msg, dtype=np.uint8)
+        if msg.size == 0:
+            msg = np.zeros(1, np.uint8)
+        off = np.ascontiguousarray(msg_off, dtype=np.uint32)
+        valid = np.zeros(max(n, 1), np.uint8)
+        words = np.zeros(max((n + 63) // 64, 1), np.uint64)
+        rc = N.lib().cmtv_verify_secp256k1(self._h, n, _u8(pk), _u8(sig), _u8(msg),
+                                           off.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), _u8(valid),
+                                           words.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)))
+        N.check(rc, "cmtv_verify_secp256k1")
+        if bitmap:
+            return valid[:n], words[: (n + 63) // 64]
+        return valid[:n]
+
+    def verify_secp256k1_device(self, n: int, d_pk: int, d_sig: int, d_msg: int, d_off: int, d_valid: int = 0,
+                                d_bitmap: int = 0, stream: int = 0) -> None:
+        """Enqueue secp256k1 verification over device-resident buffers (keys
+        n x 33 bytes)."""
+        rc = N.lib().cmtv_verify_secp256k1_device(self._h, n, d_pk, d_sig, d_msg, d_off, d_valid or None,
+                                                  d_bitmap or None, ctypes.c_void_p(stream) if stream else None)
+        N.check(rc, "cmtv_verify_secp256k1_device")
 
     # -------------------------------------------------------------- registered keys
     def register_keys(self, pk: np.ndarray, wide: bool = False) -> "KeySet":
@@ -422,6 +458,67 @@ class Sr25519BatchVerifier:
         pk = np.frombuffer(b"".join(self._pk), np.uint8)
         sig = np.frombuffer(b"".join(self._sig), np.uint8)
         v = self.ctx.verify_sr25519(pk, sig, m, off)
+        out = [bool(x) and ok for x, ok in zip(v, self._len_ok)]
+        return all(out), out
+
+
+class Secp256k1PubKey(bytes):
+    """secp256k1.PubKey (crypto/secp256k1/secp256k1.go:148): the 33-byte
+    compressed key."""
+
+    def address(self) -> bytes:
+        """RIPEMD160(SHA256(key)), secp256k1.go:156-168 (which panics on a key
+        of another length)."""
+        if len(self) != SECP256K1_PUBKEY_SIZE:
+            raise ValueError(f"secp256k1: bad public key length: {len(self)}")
+        return ripemd160(hashlib.sha256(bytes(self)).digest())
+
+    def verify_signature(self, msg: bytes, sig: bytes, ctx: Context | None = None) -> bool:
+        """PubKey.VerifySignature (secp256k1.go:192-217) as a batch of one on
+        the GPU: len(sig) != 64 -> False; a key that is not 33 bytes raises
+        (the key codec, crypto/encoding/codec.go:53, admits no other length)."""
+        if len(sig) != SIGNATURE_SIZE:
+            return False
+        if len(self) != SECP256K1_PUBKEY_SIZE:
+            raise ValueError(f"secp256k1: bad public key length: {len(self)}")
+        ctx = ctx or default_context()
+        m, off = pack_messages([bytes(msg)])
+        v = ctx.verify_secp256k1(np.frombuffer(bytes(self), np.uint8), np.frombuffer(bytes(sig), np.uint8), m, off)
+        return bool(v[0])
+
+
+class Secp256k1BatchVerifier:
+    """Batch form of secp256k1 PubKey.VerifySignature with the BatchVerifier
+    shape (add / verify -> (bool, list[bool])); every verdict comes from the
+    GPU kernel, entries with a wrong signature length are invalid, a key that
+    is not 33 bytes raises in add()."""
+
+    def __init__(self, ctx: Context | None = None):
+        self.ctx = ctx or default_context()
+        self.reset()
+
+    def __len__(self):
+        return len(self._msgs)
+
+    def reset(self):
+        self._pk, self._sig, self._msgs, self._len_ok = [], [], [], []
+
+    def add(self, key: bytes, msg: bytes, sig: bytes) -> None:
+        if len(key) != SECP256K1_PUBKEY_SIZE:
+            raise ValueError(f"secp256k1: bad public key length: {len(key)}")
+        self._pk.append(bytes(key))
+        self._len_ok.append(len(sig) == SIGNATURE_SIZE)
+        self._sig.append(bytes(sig) if len(sig) == SIGNATURE_SIZE else bytes(SIGNATURE_SIZE))
+        self._msgs.append(bytes(msg))
+
+    def verify(self):
+        n = len(self._msgs)
+        if n == 0:
+            return True, []
+        m, off = pack_messages(self._msgs)
+        pk = np.frombuffer(b"".join(self._pk), np.uint8)
+        sig = np.frombuffer(b"".join(self._sig), np.uint8)
+        v = self.ctx.verify_secp256k1(pk, sig, m, off)
         out = [bool(x) and ok for x, ok in zip(v, self._len_ok)]
         return all(out), out
 

@@ -120,6 +120,15 @@ constexpr uint32_t kKeyedBatchScratchWordsPerSig = 40;
 hipError_t launch_verify_sr25519(uint32_t n, const void* pk, const void* sig, const void* msg, const void* off,
                                  const uint32_t* btab, uint32_t* atab, const uint32_t* prog, int nops, void* valid,
                                  void* bitmap, uint32_t kflags, hipStream_t s);
+// secp256k1 ECDSA (secp256k1.hip): the fixed table (1..128)[256^j]G, j = 0..32,
+// rows of 32 words (528 KiB), built by launch_secp_gtab_build; the lane
+// kernel's scratch, (1..8)Q at 30 words per point
+constexpr uint32_t kSecpGtabWords = 33 * 128 * 32;
+constexpr uint32_t kSecpQtabWordsPerLane = 240;
+hipError_t launch_secp_gtab_build(uint32_t* d_rows, hipStream_t s);
+// pk n x 33 bytes; qtab: n rounded up to 64, times kSecpQtabWordsPerLane words
+hipError_t launch_verify_secp256k1(uint32_t n, const void* pk, const void* sig, const void* msg, const void* off,
+                                   const uint32_t* gtab, uint32_t* qtab, void* valid, void* bitmap, hipStream_t s);
 hipError_t launch_sign_bytes(uint32_t n, const void* tmpls, const uint8_t* blob, const uint32_t* tidx,
                              const uint8_t* commit_flag, const int64_t* sec, const int32_t* nanos,
                              const uint32_t* off, uint8_t* msg, hipStream_t s);

@@ -424,6 +424,11 @@ struct CmtvDev {
   hipStream_t stream = nullptr;
   uint32_t* d_btab = nullptr;
   uint32_t* d_srprog = nullptr;  // sr25519 transcript: the sponge after the constant prefix (merlin.h)
+  // secp256k1: the fixed table (kernels.h kSecpGtabWords), built by the first
+  // secp256k1 batch of the context (ensure_secp_gtab), and the host-buffer
+  // call's own staging (no other entry point touches them)
+  uint32_t* d_secp_gtab = nullptr;
+  DevBuf secp_in, secp_out;
   DevBuf d_in, d_out, d_all;
   HostBuf h_in, h_out;
   // small single-device host batches: the kernel writes the verdict bitmap
@@ -1752,6 +1757,107 @@ static int single_device_rc(cmtv_ctx* ctx, int rc) {
   return rc;
 }
 
+// ---------------------------------------------------------------- secp256k1
+// ECDSA over secp256k1 (secp256k1.hip): one lane kernel, on devs[0] only; no
+// verdict cache, no registered keys, no sharding.
+
+// The fixed table of G's multiples, built on the device by the context's
+// first secp256k1 batch (cmtv_open's cost and footprint stay as they were).
+// Built on D's own stream and waited for, so launches on any stream may read it.
+static hipError_t ensure_secp_gtab(CmtvDev& D) {
+  if (D.d_secp_gtab) return hipSuccess;
+  uint32_t* t = nullptr;
+  hipError_t e = hipMalloc(&t, (size_t)kSecpGtabWords * sizeof(uint32_t));
+  if (e != hipSuccess) return e;
+  e = launch_secp_gtab_build(t, D.stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(D.stream);
+  if (e != hipSuccess) {
+    (void)hipFree(t);
+    return e;
+  }
+  D.d_secp_gtab = t;
+  return hipSuccess;
+}
+
+// Enqueue verification of n secp256k1 signatures whose inputs are in device
+// memory of device D (current on this thread): pk n x 33 bytes.
+static int enqueue_verify_secp(cmtv_ctx* ctx, CmtvDev& D, size_t n, const uint8_t* d_pk, const uint8_t* d_sig,
+                               const uint8_t* d_msg, const uint32_t* d_off, uint8_t* d_valid, uint64_t* d_bitmap,
+                               hipStream_t s) {
+  if (n == 0) return CMTV_OK;
+  if (fault_hit(ctx) || D.inject_fault) return CMTV_EHIP;
+  hipError_t e = ensure_secp_gtab(D);
+  if (e != hipSuccess) return hip_fail(e);
+  Scratch& S = D.scratch;
+  const size_t chunk = ctx->lane_chunk;
+  const size_t lanes_padded = (std::min<size_t>(n, chunk) + 63) / 64 * 64;
+  if ((e = acquire_scratch(S, lanes_padded * kSecpQtabWordsPerLane * sizeof(uint32_t), s)) != hipSuccess)
+    return hip_fail(e);
+  D.timing.harvest(ctx->stats, D.device_ms, D.timed_calls, false);
+  Timing::Pair tp;
+  const bool timed = ctx->timing_every && D.timing_seq++ % ctx->timing_every == 0;
+  if (timed && (e = D.timing.begin(tp, s)) != hipSuccess) return hip_fail(e);
+  for (size_t c = 0; c < n; c += chunk) {
+    const uint32_t cn = (uint32_t)std::min<size_t>(chunk, n - c);
+    e = launch_verify_secp256k1(cn, d_pk + 33 * c, d_sig + 64 * c, d_msg, d_off + c, D.d_secp_gtab,
+                                static_cast<uint32_t*>(S.buf.p), d_valid ? d_valid + c : nullptr,
+                                d_bitmap ? d_bitmap + c / 64 : nullptr, s);
+    if (e != hipSuccess) {
+      D.timing.abandon(tp);
+      return hip_fail(e);
+    }
+    ctx->stats.kernel_launches++;
+    D.launches++;
+  }
+  if ((e = release_scratch(S, s)) != hipSuccess) return hip_fail(e);
+  if (timed && (e = D.timing.end(tp, s)) != hipSuccess) return hip_fail(e);
+  ctx->stats.calls++;
+  ctx->stats.signatures += n;
+  D.calls++;
+  D.signatures += n;
+  return CMTV_OK;
+}
+
+// Host buffers in, verdicts out, on devs[0] (caller holds the context lock):
+// one staging block pk | sig | off | msg, the verdict bitmap back.
+static int verify_secp_host_locked(cmtv_ctx* ctx, size_t n, const uint8_t* pk, const uint8_t* sig,
+                                   const uint8_t* msg, const uint32_t* msg_off, uint8_t* out_valid,
+                                   uint64_t* out_bitmap) {
+  CmtvDev& D = ctx->devs[0];
+  const size_t msg_bytes = msg_off[n];
+  const size_t o_sig = align_up(33 * n, 16), o_off = o_sig + 64 * n, o_msg = o_off + 4 * (n + 1);
+  const size_t words = (n + 63) / 64;
+  hipError_t e;
+  // +4: the kernel's aligned reads end inside the last message byte's word
+  if ((e = D.secp_in.ensure(o_msg + msg_bytes + 4)) != hipSuccess) return hip_fail(e);
+  if ((e = D.secp_out.ensure(8 * words)) != hipSuccess) return hip_fail(e);
+  auto* din = static_cast<uint8_t*>(D.secp_in.p);
+  hipStream_t s = D.stream;
+  if ((e = hipMemcpyAsync(din, pk, 33 * n, hipMemcpyHostToDevice, s)) != hipSuccess) return hip_fail(e);
+  if ((e = hipMemcpyAsync(din + o_sig, sig, 64 * n, hipMemcpyHostToDevice, s)) != hipSuccess) return hip_fail(e);
+  if ((e = hipMemcpyAsync(din + o_off, msg_off, 4 * (n + 1), hipMemcpyHostToDevice, s)) != hipSuccess)
+    return hip_fail(e);
+  if (msg_bytes && (e = hipMemcpyAsync(din + o_msg, msg, msg_bytes, hipMemcpyHostToDevice, s)) != hipSuccess)
+    return hip_fail(e);
+  auto* dbm = static_cast<uint64_t*>(D.secp_out.p);
+  const int rc = enqueue_verify_secp(ctx, D, n, din, din + o_sig, din + o_msg,
+                                     reinterpret_cast<const uint32_t*>(din + o_off), nullptr, dbm, s);
+  if (rc != CMTV_OK) {
+    (void)hipStreamSynchronize(s);  // the copies read the caller's buffers
+    return rc;
+  }
+  std::vector<uint64_t> bm(words);
+  if ((e = hipMemcpyAsync(bm.data(), dbm, 8 * words, hipMemcpyDeviceToHost, s)) != hipSuccess) return hip_fail(e);
+  if ((e = wait_stream(ctx, s)) != hipSuccess) return hip_fail(e);
+  size_t valid_count = 0;
+  for (size_t w = 0; w < words; w++) valid_count += (size_t)__builtin_popcountll(bm[w]);
+  ctx->stats.invalid += n - valid_count;
+  if (out_bitmap) std::memcpy(out_bitmap, bm.data(), 8 * words);
+  if (out_valid)
+    for (size_t i = 0; i < n; i++) out_valid[i] = (uint8_t)((bm[i >> 6] >> (i & 63)) & 1);
+  return CMTV_OK;
+}
+
 // Early-staged signatures (stage_sigs_early_locked) are valid only inside the
 // lock hold of the cmtv_verify_commit call that staged them: every new hold
 // forgets them, so a later call can never take stale device bytes for its own
@@ -1832,6 +1938,10 @@ static void release_device(CmtvDev& D) {
   D.h_zin.release();
   if (D.d_btab) (void)hipFree(D.d_btab);
   if (D.d_srprog) (void)hipFree(D.d_srprog);
+  if (D.d_secp_gtab) (void)hipFree(D.d_secp_gtab);
+  D.d_secp_gtab = nullptr;
+  D.secp_in.release();
+  D.secp_out.release();
   if (D.d_diag) (void)hipFree(D.d_diag);
   D.d_diag = nullptr;
   if (D.d_rowslots) (void)hipFree(D.d_rowslots);
@@ -2304,6 +2414,34 @@ int cmtv_verify_sr25519_device(cmtv_ctx* ctx, size_t n, const void* d_pk, const 
                           static_cast<const uint8_t*>(d_msg), static_cast<const uint32_t*>(d_msg_off), kModeSr25519,
                           static_cast<uint8_t*>(d_valid), static_cast<uint64_t*>(d_bitmap),
                           static_cast<hipStream_t>(stream)));
+}
+
+int cmtv_verify_secp256k1(cmtv_ctx* ctx, size_t n, const uint8_t* pk, const uint8_t* sig, const uint8_t* msg,
+                          const uint32_t* msg_off, uint8_t* out_valid, uint64_t* out_bitmap) {
+  if (!ctx || n > (1ull << 31)) return CMTV_EINVAL;
+  if (n == 0) return CMTV_OK;
+  if (!pk || !sig || !msg_off || (!msg && msg_off[n] != 0) || (!out_valid && !out_bitmap)) return CMTV_EINVAL;
+  for (size_t i = 0; i < n; i++)
+    if (msg_off[i + 1] < msg_off[i]) return CMTV_EINVAL;
+  std::unique_lock<std::mutex> lk;
+  if (ctx_lock(ctx, lk) != CMTV_OK) return CMTV_ENODEV;
+  if (dev0_usable(ctx) != CMTV_OK) return CMTV_ENODEV;
+  return single_device_rc(ctx, verify_secp_host_locked(ctx, n, pk, sig, msg, msg_off, out_valid, out_bitmap));
+}
+
+int cmtv_verify_secp256k1_device(cmtv_ctx* ctx, size_t n, const void* d_pk, const void* d_sig, const void* d_msg,
+                                 const void* d_msg_off, void* d_valid, void* d_bitmap, void* stream) {
+  if (!ctx || n > (1ull << 31)) return CMTV_EINVAL;
+  if (n == 0) return CMTV_OK;
+  if (!d_pk || !d_sig || !d_msg || !d_msg_off || (!d_valid && !d_bitmap)) return CMTV_EINVAL;
+  std::unique_lock<std::mutex> lk;
+  if (ctx_lock(ctx, lk) != CMTV_OK) return CMTV_ENODEV;
+  if (dev0_usable(ctx) != CMTV_OK) return CMTV_ENODEV;
+  return single_device_rc(
+      ctx, enqueue_verify_secp(ctx, ctx->devs[0], n, static_cast<const uint8_t*>(d_pk),
+                               static_cast<const uint8_t*>(d_sig), static_cast<const uint8_t*>(d_msg),
+                               static_cast<const uint32_t*>(d_msg_off), static_cast<uint8_t*>(d_valid),
+                               static_cast<uint64_t*>(d_bitmap), static_cast<hipStream_t>(stream)));
 }
 
 }  // extern "C"

@@ -1,0 +1,121 @@
+// secp256k1.hip -- gfx950 kernels for secp256k1 ECDSA batch verification
+// (reference path crypto/secp256k1/secp256k1.go:192-217).
+//
+//   k_verify_secp256k1: one signature per lane (secp256k1.h secp_verify_one):
+//     key decompression, scalars mod n, SHA-256 of the lane's message,
+//     [r/s]Q by signed 4-bit windows over a per-lane table and [e/s]G from
+//     the fixed comb table, projective comparison; a wavefront ballot packs
+//     64 verdicts into one bitmap word.
+//   k_secp_gtab_build: the fixed table (1..128)[256^j]G, one row per thread;
+//     the runtime runs it once per context, on the first secp256k1 batch.
+//
+// Memory layout: pk n x 33 B and sig n x 64 B (read bytewise: a 33-byte
+// stride has no alignment), msg flat bytes + (n+1) u32 offsets as the other
+// kernels. The per-lane table (1..8)Q lives in the launch's scratch,
+// word-major / lane-minor (word w of entry e for lane l at
+// (e * 30 + w) * stride + l), so a wave's access to one word is one 256-byte
+// line whenever its lanes pick the same entry. The fixed table's rows are
+// 32 words (16-byte aligned): a lane gathers its row with dwordx4 loads.
+#include <hip/hip_runtime.h>
+
+#include "kernels.h"
+#include "secp256k1.h"
+
+namespace cmtv {
+
+static_assert(kSecpQtabWordsPerLane == SECP_QTAB_ENTRIES * SECP_PT_WORDS, "scratch per lane");
+static_assert(kSecpGtabWords == (uint32_t)SECP_GTAB_ENTRIES * SECP_GTAB_ROW_WORDS, "fixed table size");
+
+struct DevSecpQTab {
+  uint32_t* __restrict__ base;
+  uint32_t stride;
+  uint32_t lane;
+  __device__ __forceinline__ void store(int e, const pt256& p) {
+    uint32_t* q = base + (size_t)(e * SECP_PT_WORDS) * stride + lane;
+#pragma unroll
+    for (int i = 0; i < 10; i++) {
+      q[(size_t)i * stride] = p.X.v[i];
+      q[(size_t)(10 + i) * stride] = p.Y.v[i];
+      q[(size_t)(20 + i) * stride] = p.Z.v[i];
+    }
+  }
+  __device__ __forceinline__ void load(int e, pt256& p) const {
+    const uint32_t* q = base + (size_t)(e * SECP_PT_WORDS) * stride + lane;
+#pragma unroll
+    for (int i = 0; i < 10; i++) {
+      p.X.v[i] = q[(size_t)i * stride];
+      p.Y.v[i] = q[(size_t)(10 + i) * stride];
+      p.Z.v[i] = q[(size_t)(20 + i) * stride];
+    }
+  }
+};
+
+struct DevSecpGTab {
+  const uint32_t* __restrict__ rows;
+  __device__ __forceinline__ void load(int row, pt256& p) const {
+    const uint4* q = reinterpret_cast<const uint4*>(rows + (size_t)row * SECP_GTAB_ROW_WORDS);
+    uint32_t w[32];
+#pragma unroll
+    for (int k = 0; k < 8; k++) {
+      const uint4 v = q[k];
+      w[4 * k] = v.x;
+      w[4 * k + 1] = v.y;
+      w[4 * k + 2] = v.z;
+      w[4 * k + 3] = v.w;
+    }
+#pragma unroll
+    for (int i = 0; i < 10; i++) {
+      p.X.v[i] = w[i];
+      p.Y.v[i] = w[10 + i];
+      p.Z.v[i] = w[20 + i];
+    }
+  }
+};
+
+__global__ __launch_bounds__(64) void k_secp_gtab_build(uint32_t* __restrict__ rows) {
+  const uint32_t gid = blockIdx.x * 64 + threadIdx.x;
+  if (gid >= (uint32_t)SECP_GTAB_ENTRIES) return;
+  uint32_t row[SECP_GTAB_ROW_WORDS];
+  secp_gtab_row(row, (int)(gid / SECP_GTAB_PER_POS), (int)(gid % SECP_GTAB_PER_POS) + 1);
+  uint4* out = reinterpret_cast<uint4*>(rows + (size_t)gid * SECP_GTAB_ROW_WORDS);
+#pragma unroll
+  for (int k = 0; k < 8; k++) out[k] = make_uint4(row[4 * k], row[4 * k + 1], row[4 * k + 2], row[4 * k + 3]);
+}
+
+__global__ __launch_bounds__(64, 2) void k_verify_secp256k1(uint32_t n, const uint8_t* __restrict__ pk,
+                                                            const uint8_t* __restrict__ sig,
+                                                            const uint8_t* __restrict__ msg,
+                                                            const uint32_t* __restrict__ off,
+                                                            const uint32_t* __restrict__ gtab,
+                                                            uint32_t* __restrict__ qtab,
+                                                            uint8_t* __restrict__ out_valid,
+                                                            uint64_t* __restrict__ out_bitmap) {
+  const uint32_t gid = blockIdx.x * 64 + threadIdx.x;
+  const bool active = gid < n;
+  const uint32_t i = active ? gid : n - 1;
+  const uint32_t m0 = off[i], m1 = off[i + 1];
+  DevSecpQTab qt{qtab, gridDim.x * 64u, gid};
+  DevSecpGTab gt{gtab};
+  bool v = secp_verify_one(pk + 33 * (size_t)i, sig + 64 * (size_t)i, msg + m0, m1 - m0, qt, gt);
+  v = v && active;
+  if (active && out_valid) out_valid[gid] = v ? 1 : 0;
+  const uint64_t mask = __ballot(v);
+  if (threadIdx.x == 0 && out_bitmap) out_bitmap[gid >> 6] = mask;
+}
+
+hipError_t launch_secp_gtab_build(uint32_t* d_rows, hipStream_t s) {
+  hipLaunchKernelGGL(k_secp_gtab_build, dim3((SECP_GTAB_ENTRIES + 63) / 64), dim3(64), 0, s, d_rows);
+  return hipGetLastError();
+}
+
+hipError_t launch_verify_secp256k1(uint32_t n, const void* pk, const void* sig, const void* msg, const void* off,
+                                   const uint32_t* gtab, uint32_t* qtab, void* valid, void* bitmap, hipStream_t s) {
+  if (n == 0) return hipSuccess;
+  hipLaunchKernelGGL(k_verify_secp256k1, dim3((n + 63) / 64), dim3(64), 0, s, n, static_cast<const uint8_t*>(pk),
+                     static_cast<const uint8_t*>(sig), static_cast<const uint8_t*>(msg),
+                     static_cast<const uint32_t*>(off), gtab, qtab, static_cast<uint8_t*>(valid),
+                     static_cast<uint64_t*>(bitmap));
+  return hipGetLastError();
+}
+
+}  // namespace cmtv

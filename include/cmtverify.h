@@ -305,6 +305,33 @@ int cmtv_verify_sr25519(cmtv_ctx* ctx, size_t n, const uint8_t* pk, const uint8_
 int cmtv_verify_sr25519_device(cmtv_ctx* ctx, size_t n, const void* d_pk, const void* d_sig, const void* d_msg,
                                const void* d_msg_off, void* d_valid, void* d_bitmap, void* stream);
 
+/* ------------------------------------------------------------ secp256k1 */
+
+/* secp256k1 ECDSA batch verification: the other key type of the reference's
+ * key codec (crypto/encoding/codec.go:20-63). Each verdict equals
+ *   secp256k1.PubKey(pk_i).VerifySignature(msg_i, sig_i)   crypto/secp256k1/secp256k1.go:192-217
+ * (btcec v2.2.1: the key is a 33-byte compressed point, prefix 0x02 / 0x03,
+ * x < p not reduced, on the curve; the signature is r || s, 32 big-endian
+ * bytes each, both reduced mod n when their bytes are >= n, r != 0, s != 0
+ * and s <= (n - 1) / 2, the lower-S rule; e = SHA-256(msg); accepted iff
+ * X = [e/s]G + [r/s]Q is not infinity and X.x mod n = r) for 33-byte keys
+ * (pk is n x 33 bytes) and 64-byte signatures. Callers apply the length rule
+ * (len(sig) != 64 -> false). The 65-byte uncompressed and hybrid key
+ * encodings btcec's ParsePubKey also takes never pass the key codec
+ * (codec.go:53) and are not supported.
+ * Runs on the context's first device (CMTV_ENODEV once it is retired), in
+ * launches of at most CMTV_LANE_CHUNK signatures. The verdict cache and the
+ * keyset cache do not apply. The first call of a context builds the fixed
+ * table of G's multiples on the device (528 KiB). Buffers, ownership and
+ * blocking behaviour as cmtv_verify_sr25519. */
+int cmtv_verify_secp256k1(cmtv_ctx* ctx, size_t n, const uint8_t* pk, const uint8_t* sig, const uint8_t* msg,
+                          const uint32_t* msg_off, uint8_t* out_valid, uint64_t* out_bitmap);
+
+/* Same with device-resident inputs, enqueued on `stream` (as
+ * cmtv_verify_sr25519_device); d_valid and d_bitmap are each optional. */
+int cmtv_verify_secp256k1_device(cmtv_ctx* ctx, size_t n, const void* d_pk, const void* d_sig, const void* d_msg,
+                                 const void* d_msg_off, void* d_valid, void* d_bitmap, void* stream);
+
 /* ------------------------------------------------------------ registered keys */
 
 /* A validator set signs commit after commit with the same keys (blocksync,
