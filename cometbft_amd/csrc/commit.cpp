@@ -237,7 +237,7 @@ bool templated_enabled() {
 // plans it and writes the per-signature flag (the caller's key, signature and
 // timestamp arrays are the batch; no message offsets: every message is at
 // most msg_len_bound bytes, and the fused kernels the runtime picks for such
-// a batch build each message from the template -- runtime.cpp
+// a batch build each message from the template -- host_batch.cpp
 // verify_templated_locked derives the offsets for any other form).
 // False (B left empty) sends it down the general path.
 bool job_prepare_fast(CommitJob& J, SigBatch& B) {
@@ -609,7 +609,7 @@ int job_replay_batch(CommitJob& J, const std::vector<uint8_t>& all_valid, Seen& 
 // discarded (after the kernel finishes) and the normal path runs. Returns
 // true with *rc set when the speculation was taken.
 bool verify_commit_spec(cmtv_ctx* ctx, const CommitJob& J0, uint32_t mode, Seen& seen, int* rc) {
-  // the context's threshold (runtime.cpp spec_min: 0 = off)
+  // the context's threshold (keyset.cpp spec_min: 0 = off)
   const uint32_t kSpecMin = cmtv::spec_min(ctx);
   const cmtv_valset* vals = J0.vals;
   const cmtv_commit* c = J0.commit;

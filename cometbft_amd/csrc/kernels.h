@@ -14,7 +14,7 @@ constexpr uint32_t kCombWords = 32 * 128 * 32;     // one registered-key comb (k
 constexpr uint32_t kCombScratchWordsPerKey = 128 * 320;  // prefix products while building
 
 // The verification forms (launch_verify / launch_verify_sr25519 kflags bits
-// 0..7; the runtime picks one per batch size, runtime.cpp ed_form / sr_form):
+// 0..7; the runtime picks one per batch size, runtime_state.h ed_form / sr_form):
 //   kFormLane : one signature per lane (k_verify, k_verify_sr25519)
 //   kFormQuad : four lanes per signature, three quad waves + a helper wave
 //               that hashes and sums each window's table entries
@@ -39,7 +39,7 @@ constexpr uint32_t kKeyedRow = 0, kKeyedQuad = 1, kKeyedLane = 2;
 // two-bit verdict fields: kernels.hip row_bitmap_add); the wave that fills a
 // word's last field writes that word's 32 bitmap bits and zeroes it. A slot is
 // reused after kRowSlots further row launches on the device; the runtime
-// fences a reuse against the slot's previous launch (runtime.cpp
+// fences a reuse against the slot's previous launch (launch.cpp
 // row_slot_acquire). kRowMaxCap bounds a row launch.
 constexpr uint32_t kRowSlots = 256, kRowSlotWords = 1024, kRowMaxCap = 4 * (kRowSlotWords - 16);
 // A row launch's ring slot and, optionally, its tagged bitmap: with tagged
@@ -48,7 +48,7 @@ constexpr uint32_t kRowSlots = 256, kRowSlotWords = 1024, kRowMaxCap = 4 * (kRow
 // tagged[j] with ONE 64-bit system-scope atomic store instead of writing the
 // bitmap, so the host knows the bitmap is complete when every entry carries
 // seq -- without waiting for the kernel to retire, and without any ordering
-// between the waves' stores (runtime.cpp wait_row_tags). The slot word is zero
+// between the waves' stores (host_batch.cpp wait_row_tags). The slot word is zero
 // again before its entry is stored.
 struct RowSlot {
   uint32_t* words = nullptr;

@@ -6,7 +6,7 @@
 // thread with the context lock held throughout, and stages the whole batch
 // before the first kernel starts. Here a call is cut into chunks of about
 // CMTV_PIPE_CHUNK planned signatures (commit-aligned, one registered key set
-// per chunk) that flow through the per-device bulk lanes (runtime.cpp):
+// per chunk) that flow through the per-device bulk lanes (bulk_lane.cpp):
 //
 //   plan     every commit's preamble and plan (the signatures the reference
 //            loop can reach: types/validator_set.go:685-707, 740-762,

@@ -1,5 +1,6 @@
-// runtime_internal.h -- functions shared between runtime.cpp and the host-side
-// commit / batch layers (commit.cpp). Not part of the C ABI.
+// runtime_internal.h -- functions shared between the runtime (runtime.cpp and
+// the files beside it that include runtime_state.h) and the host-side commit /
+// batch layers (commit.cpp, pipeline.cpp). Not part of the C ABI.
 #pragma once
 #include <stdint.h>
 #include <stddef.h>
@@ -156,13 +157,13 @@ struct PipeConfig {
   bool split_submit = true;
 };
 PipeConfig pipe_config(const cmtv_ctx* ctx);
-// Latency calls beside the pipeline (runtime.cpp cmtv_ctx::lat_window_ns):
+// Latency calls beside the pipeline (runtime_state.h cmtv_ctx::lat_window_ns):
 // note_latency marks one (a single commit, a small batch); latency_recent is
 // true within the window after one -- the pipeline then submits its chunks
 // to the CU-masked exec stream (BulkLayout::masked). BulkBusy marks a
 // pipeline call in flight (its scope).
 void note_latency(cmtv_ctx* ctx);
-// CMTV_CALL_TRACE (diagnostics, runtime.cpp cmtv_ctx::call_trace)
+// CMTV_CALL_TRACE (diagnostics, runtime_state.h cmtv_ctx::call_trace)
 bool call_trace_on(const cmtv_ctx* ctx);
 uint64_t call_trace_now();
 void call_trace_begin_locked(cmtv_ctx* ctx);

@@ -1,5 +1,5 @@
 // shard.h -- how a host batch is split across the devices of a context
-// (runtime.cpp). Plain C++, shared with the host test
+// (host_batch.cpp). Plain C++, shared with the host test
 // tests/host/shardcheck.cpp.
 //
 // G devices take contiguous shards of S signatures each, S a multiple of 64,

@@ -34,7 +34,7 @@ struct SbTemplate {
 };
 
 // One commit of a direct cross-height chunk (pipeline.cpp with the caller's
-// arguments in cmtv_alloc_pinned memory; runtime.cpp bulk_submit_locked;
+// arguments in cmtv_alloc_pinned memory; bulk_lane.cpp bulk_submit_locked;
 // k_bulk_gather): where the commit's arrays landed in the chunk's device copy
 // of the caller's pinned arena (byte offsets), and its plan, which is the
 // commit's signatures [0, m) -- batch indices [sp, sp + m). Its template and

@@ -167,7 +167,7 @@ typedef struct cmtv_device_stats {
  * the helper-summed kernel's helper adds the top k of [u]B's 16 comb
  * positions, default 6), CMTV_HOST_POLL=0 (a small single-device host batch
  * on a row kernel waits for its stream instead of polling the kernel's tagged
- * bitmap words: runtime.cpp wait_row_tags; the call may otherwise return
+ * bitmap words: host_batch.cpp wait_row_tags; the call may otherwise return
  * while the kernel's last waves retire, its verdicts already complete). */
 int cmtv_open(const cmtv_config* cfg, cmtv_ctx** out);
 

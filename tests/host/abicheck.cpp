@@ -1,4 +1,4 @@
-// Sanitizer driver for the host side of libcmtverify (runtime.cpp,
+// Sanitizer driver for the host side of libcmtverify (runtime.cpp and the files beside it,
 // commit.cpp): built with host-only AddressSanitizer + UBSan
 // (cometbft_amd/csrc/Makefile target `san`), linked with the same gfx950
 // kernel objects, and driven through the public C ABI only. Test

@@ -231,7 +231,7 @@ const cmtv_keyset* keyset_for_locked(cmtv_ctx* ctx, const uint8_t* pk32, size_t 
   ks->pk.assign(pk32, pk32 + 32 * n_keys);
   if (ctx->keysets.size() >= ctx->keyset_cap) {
     // the real cache frees an evicted set once no call has it pinned
-    // (runtime.cpp evict_keyset_locked); the fake keeps every one until close
+    // (keyset.cpp evict_keyset_locked); the fake keeps every one until close
     ctx->evicted.push_back(ctx->keysets.front().second);
     ctx->keysets.erase(ctx->keysets.begin());
   }
@@ -315,7 +315,7 @@ int bulk_submit_locked(cmtv_ctx* ctx, size_t dev, int slot, const BulkLayout& L,
   return CMTV_OK;
 }
 
-// A direct chunk, as the device sees it (runtime.cpp bulk_submit_locked,
+// A direct chunk, as the device sees it (bulk_lane.cpp bulk_submit_locked,
 // signbytes.hip k_bulk_gather / k_bulk_bases / k_bulk_rebase): the spans of
 // the caller's pinned memory copied to o_arena, then the per-signature layout
 // built from the descriptors -- into the slot's buffer, grown to dev_bytes,
@@ -442,7 +442,7 @@ void bulk_drain(cmtv_ctx* ctx) {
 }
 
 bool retire_device_locked(cmtv_ctx* ctx, size_t dev) {
-  if (ctx->failed[dev]) return !ctx->live.empty();  // as runtime.cpp
+  if (ctx->failed[dev]) return !ctx->live.empty();  // as gather.cpp
   if (ctx->live.size() < 2) return false;
   ctx->failed[dev] = true;
   for (size_t i = 0; i < ctx->live.size(); i++)

@@ -1,5 +1,5 @@
 // rccl_stub.cpp -- test double of the five RCCL entry points libcmtverify
-// resolves with dlopen (runtime.cpp load_rccl), for rehearsing the library's
+// resolves with dlopen (gather.cpp load_rccl), for rehearsing the library's
 // multi-rank code on a one-GPU box. Selected per context
 // by CMTV_RCCL_LIB=<path to librccl_stub.so> together with CMTV_FORCE_RCCL=1
 // over a repeated device ordinal. Test infrastructure: nothing in the product

@@ -139,7 +139,7 @@ def test_open_devices_without_gpu_is_enodev():
 
 def test_rccl_stub_exports_what_the_library_binds():
     """tests/host/librccl_stub.so (the multi-rank rehearsal's RCCL double,
-    selected by CMTV_RCCL_LIB) exports the five entry points runtime.cpp
+    selected by CMTV_RCCL_LIB) exports the five entry points gather.cpp
     load_rccl resolves, and rejects bad arguments like RCCL (no device
     work: a NULL communicator list is ncclInvalidArgument)."""
     path = os.path.join(ROOT, "tests", "host", "librccl_stub.so")
@@ -149,7 +149,7 @@ def test_rccl_stub_exports_what_the_library_binds():
     syms = {"ncclCommInitAll", "ncclCommDestroy", "ncclAllGather", "ncclGroupStart", "ncclGroupEnd", "ncclCommAbort"}
     for sym in syms:
         assert hasattr(stub, sym), sym
-    src = open(os.path.join(ROOT, "cometbft_amd", "csrc", "runtime.cpp")).read()
+    src = open(os.path.join(ROOT, "cometbft_amd", "csrc", "gather.cpp")).read()
     bound = set(re.findall(r'dlsym\(h, "(nccl[A-Za-z]+)"\)', src))
     assert bound == syms
     assert stub.ncclCommInitAll(None, 2, None) == 4  # ncclInvalidArgument

@@ -287,7 +287,7 @@ def test_latency_calls_beside_a_pipeline(n_vals, devices):
     """VerifyCommit while another thread runs a pipelined cmtv_verify_commits
     on the same context (consensus beside blocksync, round 6): the call runs
     on the device's latency stream -- the CUs the pipeline's masked chunks
-    leave free (runtime.cpp LatencyStreams) -- in its under-load form (the
+    leave free (bulk_lane.cpp LatencyStreams) -- in its under-load form (the
     registered-key quad kernel, polled through its tagged slices). Every
     outcome equals the same call's on the idle context (clean, a flipped
     signature, a wrong height), every load pass's outcomes are the reference

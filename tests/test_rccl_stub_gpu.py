@@ -1,6 +1,6 @@
 """The library's multi-rank RCCL code, executed on one GPU.
 
-libcmtverify resolves RCCL with dlopen (runtime.cpp load_rccl). With
+libcmtverify resolves RCCL with dlopen (gather.cpp load_rccl). With
 CMTV_RCCL_LIB pointing at tests/host/librccl_stub.so -- a test double of
 ncclCommInitAll / ncclGroupStart / ncclGroupEnd / ncclAllGather /
 ncclCommDestroy that gathers with ordered device copies and logs every call

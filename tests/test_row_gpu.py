@@ -1,6 +1,6 @@
 """The one-signature-per-wave row kernel (cometbft_amd/csrc/row.h,
 k_verify_row_split) and its four-wave form (k_verify_row4_split): the
-production kernels for Ed25519 batches up to 1,536 signatures (runtime.cpp
+production kernels for Ed25519 batches up to 1,536 signatures (runtime_state.h
 kRowMax; 256 and below on the four-wave form), i.e. the 150-validator
 VerifyCommit.
 
@@ -194,7 +194,7 @@ def test_row_kernels_on_random_malformed_inputs(form_ctx, mode):
 
 def test_host_batches_read_the_completion_flag():
     """Small single-device host batches on a row kernel return when the
-    kernel's completion flag arrives (kernels.h RowSlot, runtime.cpp
+    kernel's completion flag arrives (kernels.h RowSlot, host_batch.cpp
     wait_row_done), not when the stream drains: back-to-back calls of ragged
     sizes (word and half-word edges) and both modes, plain and registered-key,
     each against the oracle bit for bit, and each counted in polled_calls; a

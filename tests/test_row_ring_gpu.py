@@ -10,7 +10,7 @@ fills the word's last field writes the word's 32 bitmap bits and zeroes it
 same fields: two rejects sum to the accept pattern. Device-resident calls
 (cmtv_verify_ed25519_device and friends) are non-blocking on the caller's
 streams, so a caller can have a launch parked behind other work while 256
-later launches wrap the ring back to its slot. runtime.cpp row_slot_acquire
+later launches wrap the ring back to its slot. launch.cpp row_slot_acquire
 fences the slot: the new launch's stream waits for the old launch's event.
 
 The race is made deterministic here, on four streams with a hardware queue
@@ -24,7 +24,7 @@ X and Y both become runnable when E fires and, 100 signatures each (one CU
 per signature), fit the chip side by side. Unfenced they add into each
 other's fields and complete each other's words; fenced, Y starts after X.
 Host-API launches that return on the polled bitmap tags are settled by an
-event the next call checks (runtime.cpp settle_polled). Oracle: oracle/liboracle.so (the C restatement of
+event the next call checks (runtime_state.h settle_polled). Oracle: oracle/liboracle.so (the C restatement of
 Go 1.19 ed25519.Verify, crypto/ed25519/ed25519.go:148)."""
 import os
 

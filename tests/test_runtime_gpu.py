@@ -1,4 +1,4 @@
-"""GPU tests of the host runtime (cometbft_amd/csrc/runtime.cpp):
+"""GPU tests of the host runtime (cometbft_amd/csrc/runtime.cpp and the files beside it):
 
   * multi-device contexts (cmtv_open_devices): a one-device
     context equals the single-device path; a context over a REPEATED
@@ -350,3 +350,66 @@ def test_safe_mul_edge_cases(gpu_ctx):
         e = x
     assert e is not None and "int64 overflow" in str(e)
     assert vals.valset.verify_commit_light_trusting(TU.CHAIN_ID, commit, (1, 2**64 - 1), ctx=gpu_ctx) is None
+
+
+def _secp_batch(n):
+    """n secp256k1 triples over 4 keys, every ninth signature with one bit of
+    s flipped, and the Python oracle's verdicts (tests/secp256k1_ref.py)."""
+    import random
+
+    import secp256k1_ref as S
+
+    rng = random.Random(6501)
+    privs = [rng.randbytes(32) for _ in range(4)]
+    pks = [S.pubkey_from_priv(p) for p in privs]
+    pk, sig, msgs, exp = [], [], [], []
+    for i in range(n):
+        m = rng.randbytes(40)
+        s = bytearray(S.sign(privs[i % 4], m, seed=b"%d" % i))
+        if i % 9 == 4 or i == n - 1:
+            s[32 + rng.randrange(32)] ^= 1 << rng.randrange(8)
+        pk.append(pks[i % 4])
+        sig.append(bytes(s))
+        msgs.append(m)
+        exp.append(int(S.verify(pks[i % 4], m, bytes(s))))
+    m, off = pack_messages(msgs)
+    return (np.frombuffer(b"".join(pk), np.uint8).reshape(-1, 33).copy(),
+            np.frombuffer(b"".join(sig), np.uint8).reshape(-1, 64).copy(), m, off, np.array(exp, np.uint8))
+
+
+@pytest.mark.parametrize("path", ["zero_copy", "gather", "no_poll", "secp256k1"])
+def test_host_bitmap_tail_through_each_caller(path):
+    """The one host tail of a verdict bitmap (verdict_bits.h bitmap_tail)
+    through each of its callers in host_batch.cpp: the single-device
+    mapped-memory branch with its polled tags and, CMTV_HOST_POLL=0, with the
+    kernel's own bitmap; the gather branch over two shards; the secp256k1
+    host call. Sizes of one word plus one bit (two plus one for the two
+    64-signature shards): verdict bytes equal the oracle's, no bit at or past
+    n is set, and cmtv_stats.invalid grows by the oracle's invalid count."""
+    env = {"gather": dict(CMTV_SHARD_MIN=64), "no_poll": dict(CMTV_HOST_POLL=0)}.get(path, {})
+    with _env(**env):
+        ctx = Context(devices=[0, 0]) if path == "gather" else Context(device=0)
+    n = 129 if path == "gather" else 65
+    if path == "secp256k1":
+        pk, sig, m, off, exp = _secp_batch(n)
+        call = lambda: ctx.verify_secp256k1(pk, sig, m, off, bitmap=True)  # noqa: E731
+    else:
+        pk, kidx, sig, m, off = _batch(n, 650 + n, flip=0.08)
+        sig[n - 1, 3] ^= 4  # the signature in the last word's only bit
+        exp = coracle.verify_batch(pk[kidx], sig, m, off, MODE_GO_STDLIB, nthreads=4)
+        call = lambda: ctx.verify(pk[kidx], sig, m, off, MODE_GO_STDLIB, bitmap=True)  # noqa: E731
+    assert 0 < int((exp == 0).sum()) < n and exp[n - 1] == 0
+    before = ctx.stats()
+    valid, words = call()
+    after = ctx.stats()
+    assert np.array_equal(valid, exp), np.nonzero(valid != exp)[0][:10]
+    bits = np.unpackbits(words.view(np.uint8), bitorder="little")
+    assert words.size == (n + 63) // 64 and np.array_equal(bits[:n], exp)
+    assert not bits[n:].any()
+    assert after["invalid"] - before["invalid"] == int((exp == 0).sum())
+    if path == "gather":
+        assert after["sharded_calls"] - before["sharded_calls"] == 1
+    if path == "zero_copy":
+        assert after["polled_calls"] - before["polled_calls"] == 1
+    if path == "no_poll":
+        assert after["polled_calls"] == before["polled_calls"]

@@ -1,7 +1,7 @@
 """Host-side AddressSanitizer + UBSan (the reference runs
 `go test -race`, tests.mk:67-70; this is the native-code counterpart).
 
- * tests/host/abicheck_san: runtime.cpp + commit.cpp built with host-only
+ * tests/host/abicheck_san: the runtime (runtime.cpp and the files beside it) + commit.cpp built with host-only
    -fsanitize=address,undefined (cometbft_amd/csrc/Makefile `san`), linked
    with the same gfx950 kernel objects, driven through the C ABI only.
    Without a GPU it checks the ENODEV path and the device-free entry points;
@@ -66,7 +66,7 @@ def test_runtime_under_asan_ubsan_on_device(tmp_path, corpus):
 
 
 def test_runtime_under_tsan_without_device(tmp_path, corpus):
-    """ThreadSanitizer build of runtime.cpp + commit.cpp + pipeline.cpp
+    """ThreadSanitizer build of the runtime + commit.cpp + pipeline.cpp
     (Makefile `tsan`, host code only): the device-free entry points."""
     import torch
 

@@ -1,6 +1,6 @@
 """Kernel time of registered-key verification vs batch size for the keyed quad
 (two-helper) and keyed lane kernels, to place the keyed quad/lane band
-(runtime.cpp kKeyedQuadMax), each forced with CMTV_FORM.
+(runtime_state.h kKeyedQuadMax), each forced with CMTV_FORM.
 
     python tools/keyed_sweep.py 4096 8192 12288 16384 24576 32768
 """

@@ -61,7 +61,7 @@ int main() {
   std::vector<uint32_t> all(words, 0), masked, reserved(words, 0);
   for (int c = 0; c < cus; c++) all[c / 32] |= 1u << (c % 32);
   masked = all;
-  for (uint32_t k = 0; k < 16; k++) {  // CUs 0, 1 of SE 0 on each XCD (runtime.cpp bulk_lane_init)
+  for (uint32_t k = 0; k < 16; k++) {  // CUs 0, 1 of SE 0 on each XCD (bulk_lane.cpp bulk_lane_init)
     const uint32_t b = ((k / 8) % 2) * 32 + (k % 8);
     masked[b / 32] &= ~(1u << (b % 32));
     reserved[b / 32] |= 1u << (b % 32);
