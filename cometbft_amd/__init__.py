@@ -8,9 +8,9 @@ the Python binding used by tests and bench.py; see DESIGN.md.
 """
 from . import _native
 from .crypto import (MODE_GO_STDLIB, MODE_ZIP215, BatchVerifier, Context, KeySet, PubKey, Secp256k1BatchVerifier,
-                     Secp256k1PubKey, Sr25519BatchVerifier, Sr25519PubKey, default_context, new_batch_verifier,
+                     Secp256k1KeySet, Secp256k1PubKey, Sr25519BatchVerifier, Sr25519PubKey, default_context, new_batch_verifier,
                      pack_messages)
 
 __all__ = ["MODE_GO_STDLIB", "MODE_ZIP215", "BatchVerifier", "Context", "KeySet", "PubKey", "Secp256k1BatchVerifier",
-           "Secp256k1PubKey", "Sr25519BatchVerifier", "Sr25519PubKey", "default_context", "new_batch_verifier",
+           "Secp256k1KeySet", "Secp256k1PubKey", "Sr25519BatchVerifier", "Sr25519PubKey", "default_context", "new_batch_verifier",
            "pack_messages", "_native"]

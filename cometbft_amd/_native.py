@@ -45,6 +45,8 @@ EXPORTS = (
     "cmtv_verify_ed25519_sharded_device", "cmtv_verify_ed25519_indexed_sharded_device", "cmtv_verify_ed25519_multi_device", "cmtv_close", "cmtv_strerror", "cmtv_abi_version", "cmtv_stats_get", "cmtv_device_stats_get", "cmtv_stream",
     "cmtv_verify_ed25519", "cmtv_verify_ed25519_device", "cmtv_verify_sr25519", "cmtv_verify_sr25519_device",
     "cmtv_verify_secp256k1", "cmtv_verify_secp256k1_device",
+    "cmtv_register_keys_secp256k1", "cmtv_secp_keyset_free", "cmtv_secp_keyset_len", "cmtv_verify_secp256k1_indexed",
+    "cmtv_verify_secp256k1_indexed_device",
     "cmtv_register_keys", "cmtv_register_keys_ex", "cmtv_keyset_free", "cmtv_keyset_len", "cmtv_verify_ed25519_indexed",
     "cmtv_verify_ed25519_indexed_device",
     "cmtv_batch_new", "cmtv_batch_add", "cmtv_batch_len", "cmtv_batch_verify", "cmtv_batch_reset",
@@ -169,6 +171,16 @@ def lib() -> ctypes.CDLL:
     L.cmtv_verify_secp256k1.restype = ctypes.c_int
     L.cmtv_verify_secp256k1_device.argtypes = [vp, sz, vp, vp, vp, vp, vp, vp, vp]
     L.cmtv_verify_secp256k1_device.restype = ctypes.c_int
+    L.cmtv_register_keys_secp256k1.argtypes = [vp, sz, _u8p, ctypes.POINTER(vp)]
+    L.cmtv_register_keys_secp256k1.restype = ctypes.c_int
+    L.cmtv_secp_keyset_free.argtypes = [vp]
+    L.cmtv_secp_keyset_free.restype = None
+    L.cmtv_secp_keyset_len.argtypes = [vp]
+    L.cmtv_secp_keyset_len.restype = sz
+    L.cmtv_verify_secp256k1_indexed.argtypes = [vp, vp, sz, u32p, _u8p, _u8p, u32p, _u8p, ctypes.POINTER(u64)]
+    L.cmtv_verify_secp256k1_indexed.restype = ctypes.c_int
+    L.cmtv_verify_secp256k1_indexed_device.argtypes = [vp, vp, sz, vp, vp, vp, vp, vp, vp, vp]
+    L.cmtv_verify_secp256k1_indexed_device.restype = ctypes.c_int
     L.cmtv_register_keys.argtypes = [vp, sz, _u8p, ctypes.POINTER(vp)]
     L.cmtv_register_keys.restype = ctypes.c_int
     L.cmtv_register_keys_ex.argtypes = [vp, sz, _u8p, ctypes.c_uint32, ctypes.POINTER(vp)]

@@ -252,6 +252,48 @@ class Context:
                                                   d_bitmap or None, ctypes.c_void_p(stream) if stream else None)
         N.check(rc, "cmtv_verify_secp256k1_device")
 
+    def register_secp256k1_keys(self, pk: np.ndarray) -> "Secp256k1KeySet":
+        """Parse n 33-byte compressed keys once and build their combs on the
+        first device (cmtv_register_keys_secp256k1; 528 KiB of HBM per key):
+        verify_secp256k1_indexed then needs no decompression and no
+        doublings. A key verification would reject registers too; its
+        signatures are invalid."""
+        return Secp256k1KeySet(self, pk)
+
+    def verify_secp256k1_indexed(self, keys: "Secp256k1KeySet", key_idx: np.ndarray, sig: np.ndarray,
+                                 msg: np.ndarray, msg_off: np.ndarray, bitmap: bool = False):
+        """Verdicts for n signatures, signature i by registered key key_idx[i];
+        same verdicts as verify_secp256k1(keys.pk[key_idx], ...)."""
+        key_idx = np.ascontiguousarray(key_idx, dtype=np.uint32).reshape(-1)
+        sig = np.ascontiguousarray(sig, dtype=np.uint8).reshape(-1, 64)
+        n = key_idx.shape[0]
+        if sig.shape[0] != n or len(msg_off) != n + 1:
+            raise ValueError("key_idx / sig / msg_off sizes disagree")
+        msg = np.ascontiguousarray(msg, dtype=np.uint8)
+        if msg.size == 0:
+            msg = np.zeros(1, np.uint8)
+        off = np.ascontiguousarray(msg_off, dtype=np.uint32)
+        valid = np.zeros(max(n, 1), np.uint8)
+        words = np.zeros(max((n + 63) // 64, 1), np.uint64)
+        u32p = ctypes.POINTER(ctypes.c_uint32)
+        rc = N.lib().cmtv_verify_secp256k1_indexed(self._h, keys.handle, n, key_idx.ctypes.data_as(u32p), _u8(sig),
+                                                   _u8(msg), off.ctypes.data_as(u32p), _u8(valid),
+                                                   words.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)))
+        N.check(rc, "cmtv_verify_secp256k1_indexed")
+        if bitmap:
+            return valid[:n], words[: (n + 63) // 64]
+        return valid[:n]
+
+    def verify_secp256k1_indexed_device(self, keys: "Secp256k1KeySet", n: int, d_key_idx: int, d_sig: int,
+                                        d_msg: int, d_off: int, d_valid: int = 0, d_bitmap: int = 0,
+                                        stream: int = 0) -> None:
+        """Enqueue registered-key secp256k1 verification over device-resident
+        buffers (d_key_idx: n uint32 in place of the key bytes)."""
+        rc = N.lib().cmtv_verify_secp256k1_indexed_device(self._h, keys.handle, n, d_key_idx, d_sig, d_msg, d_off,
+                                                          d_valid or None, d_bitmap or None,
+                                                          ctypes.c_void_p(stream) if stream else None)
+        N.check(rc, "cmtv_verify_secp256k1_indexed_device")
+
     # -------------------------------------------------------------- registered keys
     def register_keys(self, pk: np.ndarray, wide: bool = False) -> "KeySet":
         """Decode n 32-byte keys once and build their combs on the device
@@ -345,6 +387,39 @@ class KeySet:
         # collection of a cycle holding both -- the handle is only dropped
         if self._h and self.ctx.handle:
             N.lib().cmtv_keyset_free(self._h)
+        self._h = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+class Secp256k1KeySet:
+    """Registered secp256k1 keys (cmtv_secp_keyset): per-key combs resident in
+    the first device's HBM."""
+
+    def __init__(self, ctx: Context, pk: np.ndarray):
+        pk = np.ascontiguousarray(pk, dtype=np.uint8).reshape(-1, SECP256K1_PUBKEY_SIZE)
+        h = ctypes.c_void_p()
+        N.check(N.lib().cmtv_register_keys_secp256k1(ctx.handle, pk.shape[0], _u8(pk), ctypes.byref(h)),
+                "cmtv_register_keys_secp256k1")
+        self._h = h
+        self.ctx = ctx  # keeps the context alive while the key set is
+        self.pk = pk.copy()
+
+    @property
+    def handle(self):
+        return self._h
+
+    def __len__(self):
+        return N.lib().cmtv_secp_keyset_len(self._h)
+
+    def free(self):
+        # as KeySet.free: after the context was closed the handle is only dropped
+        if self._h and self.ctx.handle:
+            N.lib().cmtv_secp_keyset_free(self._h)
         self._h = None
 
     def __del__(self):

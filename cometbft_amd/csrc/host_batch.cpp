@@ -705,4 +705,39 @@ int verify_secp_host_locked(cmtv_ctx* ctx, size_t n, const uint8_t* pk, const ui
   return CMTV_OK;
 }
 
+// The same by registered keys: key_idx | sig | off | msg (the caller has
+// checked every index against the key set).
+int verify_secp_keyed_host_locked(cmtv_ctx* ctx, const cmtv_secp_keyset* ks, size_t n, const uint32_t* key_idx,
+                                  const uint8_t* sig, const uint8_t* msg, const uint32_t* msg_off, uint8_t* out_valid,
+                                  uint64_t* out_bitmap) {
+  CmtvDev& D = ctx->devs[0];
+  const size_t msg_bytes = msg_off[n];
+  const size_t o_sig = align_up(4 * n, 16), o_off = o_sig + 64 * n, o_msg = o_off + 4 * (n + 1);
+  const size_t words = (n + 63) / 64;
+  hipError_t e;
+  // +4: the kernel's aligned reads end inside the last message byte's word
+  if ((e = D.secp_in.ensure(o_msg + msg_bytes + 4)) != hipSuccess) return hip_fail(e);
+  if ((e = D.secp_out.ensure(8 * words)) != hipSuccess) return hip_fail(e);
+  auto* din = static_cast<uint8_t*>(D.secp_in.p);
+  hipStream_t s = D.stream;
+  if ((e = hipMemcpyAsync(din, key_idx, 4 * n, hipMemcpyHostToDevice, s)) != hipSuccess) return hip_fail(e);
+  if ((e = hipMemcpyAsync(din + o_sig, sig, 64 * n, hipMemcpyHostToDevice, s)) != hipSuccess) return hip_fail(e);
+  if ((e = hipMemcpyAsync(din + o_off, msg_off, 4 * (n + 1), hipMemcpyHostToDevice, s)) != hipSuccess)
+    return hip_fail(e);
+  if (msg_bytes && (e = hipMemcpyAsync(din + o_msg, msg, msg_bytes, hipMemcpyHostToDevice, s)) != hipSuccess)
+    return hip_fail(e);
+  auto* dbm = static_cast<uint64_t*>(D.secp_out.p);
+  const int rc = enqueue_verify_secp_keyed(ctx, D, ks, n, reinterpret_cast<const uint32_t*>(din), din + o_sig,
+                                           din + o_msg, reinterpret_cast<const uint32_t*>(din + o_off), nullptr, dbm, s);
+  if (rc != CMTV_OK) {
+    (void)hipStreamSynchronize(s);  // the copies read the caller's buffers
+    return rc;
+  }
+  std::vector<uint64_t> bm(words);
+  if ((e = hipMemcpyAsync(bm.data(), dbm, 8 * words, hipMemcpyDeviceToHost, s)) != hipSuccess) return hip_fail(e);
+  if ((e = wait_stream(ctx, s)) != hipSuccess) return hip_fail(e);
+  ctx->stats.invalid += bitmap_tail(bm.data(), n, out_bitmap, out_valid);
+  return CMTV_OK;
+}
+
 }  // namespace cmtv

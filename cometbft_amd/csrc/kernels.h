@@ -129,6 +129,15 @@ hipError_t launch_secp_gtab_build(uint32_t* d_rows, hipStream_t s);
 // pk n x 33 bytes; qtab: n rounded up to 64, times kSecpQtabWordsPerLane words
 hipError_t launch_verify_secp256k1(uint32_t n, const void* pk, const void* sig, const void* msg, const void* off,
                                    const uint32_t* gtab, uint32_t* qtab, void* valid, void* bitmap, hipStream_t s);
+// registered secp256k1 keys: per key a table in the fixed table's layout,
+// (1..128)[256^j]Q (kSecpGtabWords words, keys back to back), and an ok byte
+// (0: the key is rejected, its rows are the point at infinity); pk n_keys x 33
+hipError_t launch_secp_qcomb_build(uint32_t n_keys, const uint8_t* d_pk, uint8_t* d_ok, uint32_t* d_tab,
+                                   hipStream_t s);
+// key_idx: n words; an entry >= n_keys gives an invalid verdict. No scratch.
+hipError_t launch_verify_secp256k1_keyed(uint32_t n, uint32_t n_keys, const uint32_t* key_idx, const uint8_t* key_ok,
+                                         const uint32_t* qtab, const void* sig, const void* msg, const void* off,
+                                         const uint32_t* gtab, void* valid, void* bitmap, hipStream_t s);
 hipError_t launch_sign_bytes(uint32_t n, const void* tmpls, const uint8_t* blob, const uint32_t* tidx,
                              const uint8_t* commit_flag, const int64_t* sec, const int32_t* nanos,
                              const uint32_t* off, uint8_t* msg, hipStream_t s);

@@ -1,6 +1,7 @@
 // keyset.cpp -- registered key sets: the per-device comb (and wide) tables of
 // a validator set, the context's cache of them (cmtv_keyset_cache) with its
-// eviction and pins, and their ABI entry points.
+// eviction and pins, and their ABI entry points; and registered secp256k1
+// keys (cmtv_secp_keyset: per-key combs on the first device, no cache).
 #include <new>
 
 #include "runtime_state.h"
@@ -180,5 +181,49 @@ void cmtv_keyset_free(cmtv_keyset* ks) {
 }
 
 size_t cmtv_keyset_len(const cmtv_keyset* ks) { return ks ? ks->n : 0; }
+
+// secp256k1: the tables live on devs[0] only, where every secp256k1 launch runs.
+int cmtv_register_keys_secp256k1(cmtv_ctx* ctx, size_t n_keys, const uint8_t* pk, cmtv_secp_keyset** out) {
+  if (!out) return CMTV_EINVAL;
+  *out = nullptr;
+  // 528 KiB of comb per key: 65,536 keys are 33 GiB
+  if (!ctx || n_keys == 0 || n_keys > (1u << 16) || !pk) return CMTV_EINVAL;
+  std::unique_lock<std::mutex> lk;
+  if (ctx_lock(ctx, lk) != CMTV_OK) return CMTV_ENODEV;
+  CmtvDev& D = ctx->devs[0];
+  if (D.failed) return CMTV_ENODEV;
+  auto* ks = new (std::nothrow) cmtv_secp_keyset();
+  if (!ks) return CMTV_ENOMEM;
+  ks->ctx = ctx;
+  ks->n = n_keys;
+  ks->pk.assign(pk, pk + 33 * n_keys);
+  (void)hipSetDevice(D.ordinal);
+  hipError_t e = hipMalloc(&ks->d_pk, 33 * n_keys);
+  if (e == hipSuccess) e = hipMalloc(&ks->d_ok, n_keys);
+  if (e == hipSuccess) e = hipMalloc(&ks->d_tab, n_keys * (size_t)kSecpGtabWords * sizeof(uint32_t));
+  if (e == hipSuccess) e = hipMemcpyAsync(ks->d_pk, pk, 33 * n_keys, hipMemcpyHostToDevice, D.stream);
+  if (e == hipSuccess) e = launch_secp_qcomb_build((uint32_t)n_keys, ks->d_pk, ks->d_ok, ks->d_tab, D.stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(D.stream);
+  if (e != hipSuccess) {
+    cmtv_secp_keyset_free(ks);
+    return hip_fail(e);
+  }
+  *out = ks;
+  return CMTV_OK;
+}
+
+void cmtv_secp_keyset_free(cmtv_secp_keyset* ks) {
+  if (!ks) return;
+  if (!ks->ctx->devs.empty()) {
+    (void)hipSetDevice(ks->ctx->devs[0].ordinal);
+    (void)hipStreamSynchronize(ks->ctx->devs[0].stream);  // no kernel may still read the tables
+  }
+  if (ks->d_pk) (void)hipFree(ks->d_pk);
+  if (ks->d_ok) (void)hipFree(ks->d_ok);
+  if (ks->d_tab) (void)hipFree(ks->d_tab);
+  delete ks;
+}
+
+size_t cmtv_secp_keyset_len(const cmtv_secp_keyset* ks) { return ks ? ks->n : 0; }
 
 }  // extern "C"

@@ -220,8 +220,8 @@ int enqueue_verify_keyed(cmtv_ctx* ctx, CmtvDev& D, const cmtv_keyset::PerDev& K
 }
 
 // ---------------------------------------------------------------- secp256k1
-// ECDSA over secp256k1 (secp256k1.hip): one lane kernel, on devs[0] only; no
-// verdict cache, no registered keys, no sharding.
+// ECDSA over secp256k1 (secp256k1.hip): one lane kernel for key bytes and one
+// for registered keys, on devs[0] only; no verdict cache, no sharding.
 
 // The fixed table of G's multiples, built on the device by the context's
 // first secp256k1 batch (cmtv_open's cost and footprint stay as they were).
@@ -265,6 +265,29 @@ int enqueue_verify_secp(cmtv_ctx* ctx, CmtvDev& D, size_t n, const uint8_t* d_pk
     if ((e = L.launched(e)) != hipSuccess) return hip_fail(e);
   }
   return L.finish(n, &S);
+}
+
+// The same by registered keys (keyset.cpp cmtv_register_keys_secp256k1):
+// d_idx n key indices in place of the key bytes; no scratch.
+int enqueue_verify_secp_keyed(cmtv_ctx* ctx, CmtvDev& D, const cmtv_secp_keyset* ks, size_t n, const uint32_t* d_idx,
+                              const uint8_t* d_sig, const uint8_t* d_msg, const uint32_t* d_off, uint8_t* d_valid,
+                              uint64_t* d_bitmap, hipStream_t s) {
+  if (n == 0) return CMTV_OK;
+  if (fault_hit(ctx) || D.inject_fault) return CMTV_EHIP;
+  hipError_t e = ensure_secp_gtab(D);
+  if (e != hipSuccess) return hip_fail(e);
+  LaunchScope L{ctx, D, s};
+  if ((e = L.begin()) != hipSuccess) return hip_fail(e);
+  const size_t chunk = ctx->lane_chunk;
+  for (size_t c = 0; c < n; c += chunk) {
+    const uint32_t cn = (uint32_t)std::min<size_t>(chunk, n - c);
+    e = launch_verify_secp256k1_keyed(cn, (uint32_t)ks->n, d_idx + c, ks->d_ok, ks->d_tab, d_sig + 64 * c, d_msg,
+                                      d_off + c, D.d_secp_gtab, d_valid ? d_valid + c : nullptr,
+                                      d_bitmap ? d_bitmap + c / 64 : nullptr, s);
+    if ((e = L.launched(e)) != hipSuccess) return hip_fail(e);
+    ctx->stats.keyed_launches++;
+  }
+  return L.finish(n, nullptr);
 }
 
 }  // namespace cmtv

@@ -655,6 +655,32 @@ int cmtv_verify_ed25519_indexed_device(cmtv_ctx* ctx, const cmtv_keyset* ks, siz
   });
 }
 
+int cmtv_verify_secp256k1_indexed(cmtv_ctx* ctx, const cmtv_secp_keyset* ks, size_t n, const uint32_t* key_idx,
+                                  const uint8_t* sig, const uint8_t* msg, const uint32_t* msg_off,
+                                  uint8_t* out_valid, uint64_t* out_bitmap) {
+  if (!ks || ks->ctx != ctx) return CMTV_EINVAL;
+  if (!host_args_ok(ctx, 0, n, key_idx, sig, msg, msg_off, out_valid, out_bitmap)) return CMTV_EINVAL;
+  if (n == 0) return CMTV_OK;
+  for (size_t i = 0; i < n; i++)
+    if (key_idx[i] >= ks->n) return CMTV_EINVAL;
+  return on_dev0(ctx, [&](CmtvDev&) {
+    return verify_secp_keyed_host_locked(ctx, ks, n, key_idx, sig, msg, msg_off, out_valid, out_bitmap);
+  });
+}
+
+int cmtv_verify_secp256k1_indexed_device(cmtv_ctx* ctx, const cmtv_secp_keyset* ks, size_t n, const void* d_key_idx,
+                                         const void* d_sig, const void* d_msg, const void* d_msg_off, void* d_valid,
+                                         void* d_bitmap, void* stream) {
+  if (!ks || ks->ctx != ctx) return CMTV_EINVAL;
+  if (!device_args_ok(ctx, 0, n, d_key_idx, d_sig, d_msg, d_msg_off, d_valid, d_bitmap)) return CMTV_EINVAL;
+  if (n == 0) return CMTV_OK;
+  const DeviceArgs a(d_key_idx, d_sig, d_msg, d_msg_off, d_valid, d_bitmap, stream);
+  return on_dev0(ctx, [&](CmtvDev& D) {
+    return enqueue_verify_secp_keyed(ctx, D, ks, n, static_cast<const uint32_t*>(d_key_idx), a.sig, a.msg, a.off,
+                                     a.valid, a.bitmap, a.s);
+  });
+}
+
 int cmtv_alloc_pinned(cmtv_ctx* ctx, size_t bytes, void** out) {
   if (!ctx || !out || bytes == 0) return CMTV_EINVAL;
   *out = nullptr;

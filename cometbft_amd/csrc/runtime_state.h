@@ -567,6 +567,16 @@ struct cmtv_keyset {
   std::vector<uint8_t> pk;    // host copy (n x 32)
 };
 
+// Registered secp256k1 keys: on devs[0] only, as every secp256k1 launch.
+struct cmtv_secp_keyset {
+  cmtv_ctx* ctx = nullptr;
+  size_t n = 0;
+  std::vector<uint8_t> pk;    // host copy (n x 33)
+  uint8_t* d_pk = nullptr;    // n x 33, what the build kernel parsed
+  uint8_t* d_ok = nullptr;    // n flags: 0 = rejected key
+  uint32_t* d_tab = nullptr;  // n x kSecpGtabWords
+};
+
 namespace cmtv {
 
 inline int hip_fail(hipError_t e) {
@@ -665,6 +675,9 @@ int enqueue_verify_keyed(cmtv_ctx* ctx, CmtvDev& D, const cmtv_keyset::PerDev& K
 int enqueue_verify_secp(cmtv_ctx* ctx, CmtvDev& D, size_t n, const uint8_t* d_pk, const uint8_t* d_sig,
                         const uint8_t* d_msg, const uint32_t* d_off, uint8_t* d_valid, uint64_t* d_bitmap,
                         hipStream_t s);
+int enqueue_verify_secp_keyed(cmtv_ctx* ctx, CmtvDev& D, const cmtv_secp_keyset* ks, size_t n, const uint32_t* d_idx,
+                              const uint8_t* d_sig, const uint8_t* d_msg, const uint32_t* d_off, uint8_t* d_valid,
+                              uint64_t* d_bitmap, hipStream_t s);
 
 // host_batch.cpp: a host batch straight to the devices (no verdict cache),
 // generic keys or (ks) registered ones; secp256k1 on devs[0]. Lock held.
@@ -673,6 +686,9 @@ int verify_host_device(cmtv_ctx* ctx, size_t n, const uint8_t* pk, const uint8_t
                        const cmtv_keyset* ks = nullptr, const uint32_t* key_idx = nullptr);
 int verify_secp_host_locked(cmtv_ctx* ctx, size_t n, const uint8_t* pk, const uint8_t* sig, const uint8_t* msg,
                             const uint32_t* msg_off, uint8_t* out_valid, uint64_t* out_bitmap);
+int verify_secp_keyed_host_locked(cmtv_ctx* ctx, const cmtv_secp_keyset* ks, size_t n, const uint32_t* key_idx,
+                                  const uint8_t* sig, const uint8_t* msg, const uint32_t* msg_off, uint8_t* out_valid,
+                                  uint64_t* out_bitmap);
 
 // gather.cpp
 int gather_bitmaps(cmtv_ctx* ctx, const size_t* dev, size_t G, size_t W, uint64_t* const* bufs);

@@ -33,6 +33,8 @@
 //   [u1]G : signed radix-256 comb, digits in [-128, 128) from u1 + 0x80..80,
 //           plus a top carry; 33 additions from the fixed table
 //           (1..128) [256^j]G, j = 0..32 (GTab policy), no doublings
+//   registered keys (secp_verify_keyed_one): [u2]Q by the same comb over the
+//           key's own table (1..128) [256^j]Q (secp_qcomb_position)
 // Every lane does every step whatever its inputs (verification handles public
 // data: this is for wave uniformity, not constant time); a failed check only
 // clears the verdict.
@@ -204,20 +206,18 @@ CMTV_HD bool secp_parse_pubkey(pt256& q, const uint8_t* pk) {
   return ok;
 }
 
-// The whole verdict. QTab: store(e, pt) / load(e, pt), e = 0..7, this lane's
-// table of (e + 1)Q. GTab: load(row, pt), the fixed table's rows.
-template <class QTab, class GTab>
-CMTV_HD bool secp_verify_one(const uint8_t* pk, const uint8_t* sig, const uint8_t* msg, uint32_t mlen, QTab& qt,
-                             const GTab& gt) {
-  pt256 q;
-  bool ok = secp_parse_pubkey(q, pk);
+// The checks and scalars every verdict starts with (steps 2 and 3 and the
+// inversion of step 4): r, u1 = e / s, u2 = r / s; false when r or s is zero
+// or s is above (n - 1) / 2 (the scalars are then still defined: every lane
+// goes on).
+CMTV_HD bool secp_scalars(scn& r, scn& u1, scn& u2, const uint8_t* sig, const uint8_t* msg, uint32_t mlen) {
   uint32_t rw[8], sw[8];
   words_from_be32(rw, sig);
   words_from_be32(sw, sig + 32);
-  scn r, s, e, w, u1, u2;
+  scn s, e, w;
   scn_from_words(r, rw);
   scn_from_words(s, sw);
-  ok = ok && !scn_is_zero(r) && !scn_is_zero(s) && !scn_over_half(s);
+  const bool ok = !scn_is_zero(r) && !scn_is_zero(s) && !scn_over_half(s);
   uint32_t h[8], hw[8];
   sha256_msg(h, msg, mlen);
 #pragma unroll
@@ -226,6 +226,71 @@ CMTV_HD bool secp_verify_one(const uint8_t* pk, const uint8_t* sig, const uint8_
   scn_invert(w, s);
   scn_mul(u1, e, w);
   scn_mul(u2, r, w);
+  return ok;
+}
+
+// acc += [u]B for a scalar u < n and the comb table tab of B, rows (j, d) =
+// [d 256^j]B: the bytes of u + 0x80..80 read from the bottom, each minus 128,
+// are the signed digits of positions 0..31, and the carry out of bit 255 is
+// the digit of position 32. 33 additions, no doublings.
+template <class Tab>
+CMTV_HD void secp_comb_add(pt256& acc, const scn& u, const Tab& tab) {
+  uint32_t d[8];
+  uint64_t cy = 0;
+#pragma unroll
+  for (int i = 0; i < 8; i++) {
+    cy += (uint64_t)u.v[i] + 0x80808080u;
+    d[i] = (uint32_t)cy;
+    cy >>= 32;
+  }
+  pt256 t;
+#pragma unroll 1
+  for (int j = 0; j < 32; j++) {
+    const int dg = (int)(d[0] & 0xFF) - 128;
+#pragma unroll
+    for (int k = 0; k < 7; k++) d[k] = (d[k] >> 8) | (d[k + 1] << 24);
+    d[7] >>= 8;
+    const int mag = dg < 0 ? -dg : dg;
+    tab.load(j * SECP_GTAB_PER_POS + (mag ? mag - 1 : 0), t);
+    pt_signed_or_infinity(t, dg < 0, mag == 0);
+    pt_add(acc, acc, t);
+  }
+  tab.load(32 * SECP_GTAB_PER_POS, t);
+  pt_signed_or_infinity(t, false, cy == 0);
+  pt_add(acc, acc, t);
+}
+
+// The last step of every verdict: acc is not infinity and acc.x mod n = r,
+// without an inversion: X = r Z, or X = (r + n) Z when r + n < p
+CMTV_HD bool secp_x_is_r(const pt256& acc, const scn& r) {
+  fp fr, rz;
+  fp_from_words(fr, r.v);
+  fp_mul(rz, fr, acc.Z);
+  const bool eq1 = fp_equal(acc.X, rz);
+  const bool wraps = scn_words_less(r.v, [](int i) { return scn_pmn_word(i); });
+  uint32_t rn[8];
+  uint64_t cy = 0;
+#pragma unroll
+  for (int i = 0; i < 8; i++) {
+    cy += (uint64_t)r.v[i] + scn_n_word(i);
+    rn[i] = (uint32_t)cy;
+    cy >>= 32;
+  }
+  fp_from_words(fr, rn);
+  fp_mul(rz, fr, acc.Z);
+  const bool eq2 = wraps && fp_equal(acc.X, rz);
+  return !fp_is_zero(acc.Z) && (eq1 || eq2);
+}
+
+// The whole verdict. QTab: store(e, pt) / load(e, pt), e = 0..7, this lane's
+// table of (e + 1)Q. GTab: load(row, pt), the fixed table's rows.
+template <class QTab, class GTab>
+CMTV_HD bool secp_verify_one(const uint8_t* pk, const uint8_t* sig, const uint8_t* msg, uint32_t mlen, QTab& qt,
+                             const GTab& gt) {
+  pt256 q;
+  bool ok = secp_parse_pubkey(q, pk);
+  scn r, u1, u2;
+  ok = secp_scalars(r, u1, u2, sig, msg, mlen) && ok;
 
   // the lane's table (1..8)Q
   pt256 acc = q, t;
@@ -263,49 +328,64 @@ CMTV_HD bool secp_verify_one(const uint8_t* pk, const uint8_t* sig, const uint8_
     pt_add(acc, acc, t);
   }
 
-  // [u1]G: bytes of u1 + 0x80..80, least significant first
-  uint32_t d1[8];
-  cy = 0;
-#pragma unroll
-  for (int i = 0; i < 8; i++) {
-    cy += (uint64_t)u1.v[i] + 0x80808080u;
-    d1[i] = (uint32_t)cy;
-    cy >>= 32;
-  }
-#pragma unroll 1
-  for (int j = 0; j < 32; j++) {
-    const int dg = (int)(d1[0] & 0xFF) - 128;
-#pragma unroll
-    for (int k = 0; k < 7; k++) d1[k] = (d1[k] >> 8) | (d1[k + 1] << 24);
-    d1[7] >>= 8;
-    const int mag = dg < 0 ? -dg : dg;
-    gt.load(j * SECP_GTAB_PER_POS + (mag ? mag - 1 : 0), t);
-    pt_signed_or_infinity(t, dg < 0, mag == 0);
-    pt_add(acc, acc, t);
-  }
-  gt.load(32 * SECP_GTAB_PER_POS, t);
-  pt_signed_or_infinity(t, false, cy == 0);
-  pt_add(acc, acc, t);
+  // [u1]G: the comb over the fixed table
+  secp_comb_add(acc, u1, gt);
+  return secp_x_is_r(acc, r) && ok;
+}
 
-  // X.x mod n = r without an inversion: X = r Z, or X = (r + n) Z when r + n < p
-  ok = ok && !fp_is_zero(acc.Z);
-  fp fr, rz;
-  fp_from_words(fr, r.v);
-  fp_mul(rz, fr, acc.Z);
-  const bool eq1 = fp_equal(acc.X, rz);
-  const bool wraps = scn_words_less(r.v, [](int i) { return scn_pmn_word(i); });
-  uint32_t rn[8];
-  cy = 0;
+// ---------------------------------------------------------------- registered keys
+// A registered key Q has a comb table of its own in the fixed table's layout:
+// row (j, d) = [d 256^j]Q, j = 0..32, d = 1..128 (528 KiB per key). [u2]Q is
+// then 33 additions like [u1]G: no decompression, no per-lane table, no
+// doublings and no scratch.
+
+// Rows (j, 1..128) of the comb of the key pk, SECP_GTAB_PER_POS rows of
+// SECP_GTAB_ROW_WORDS words at rows: the key parsed, 8 j doublings to
+// B = [256^j]Q, then d B by repeated addition. The rows' magnitudes are the
+// ones pt_signed_or_infinity and pt_add take: (1, 2, 1) for Q itself,
+// (2, 2, 1) out of pt_double, (3, 2, 2) out of pt_add. A rejected key
+// (secp_parse_pubkey) gets the point at infinity (0 : 1 : 0) in every row;
+// returns whether the key was accepted. One thread per (key, j) when the
+// runtime registers keys (secp256k1.hip k_secp_qcomb_build); tests/host
+// builds tables the same way.
+CMTV_HD bool secp_qcomb_position(uint32_t* rows, const uint8_t* pk, int j) {
+  pt256 base, acc;
+  const bool ok = secp_parse_pubkey(base, pk);
+  pt_signed_or_infinity(base, false, !ok);
+#pragma unroll 1
+  for (int k = 0; k < 8 * j; k++) pt_double(base, base);
+  acc = base;
+#pragma unroll 1
+  for (int d = 1; d <= SECP_GTAB_PER_POS; d++) {
+    uint32_t* out = rows + (size_t)(d - 1) * SECP_GTAB_ROW_WORDS;
 #pragma unroll
-  for (int i = 0; i < 8; i++) {
-    cy += (uint64_t)r.v[i] + scn_n_word(i);
-    rn[i] = (uint32_t)cy;
-    cy >>= 32;
+    for (int i = 0; i < 10; i++) {
+      out[i] = ok ? acc.X.v[i] : 0u;
+      out[10 + i] = ok ? acc.Y.v[i] : (i == 0 ? 1u : 0u);
+      out[20 + i] = ok ? acc.Z.v[i] : 0u;
+    }
+    out[30] = out[31] = 0;
+    pt_add(acc, acc, base);
   }
-  fp_from_words(fr, rn);
-  fp_mul(rz, fr, acc.Z);
-  const bool eq2 = wraps && fp_equal(acc.X, rz);
-  return ok && (eq1 || eq2);
+  return ok;
+}
+
+// The verdict for a registered key: key_ok and qt from the key's table
+// (secp_qcomb_position), gt the fixed table. One accumulator takes the 33
+// additions of [u1]G and then the 33 of [u2]Q. (Two accumulators joined by a
+// 67th addition, for independent work within the one wave per SIMD of a small
+// batch, measured 1% slower at 10,000 and at 200,000 signatures and took 252
+// VGPRs for 198: DESIGN 4.6b.)
+template <class QTab, class GTab>
+CMTV_HD bool secp_verify_keyed_one(bool key_ok, const uint8_t* sig, const uint8_t* msg, uint32_t mlen, const QTab& qt,
+                                   const GTab& gt) {
+  scn r, u1, u2;
+  const bool ok = secp_scalars(r, u1, u2, sig, msg, mlen) && key_ok;
+  pt256 acc;
+  pt_set_infinity(acc);
+  secp_comb_add(acc, u1, gt);
+  secp_comb_add(acc, u2, qt);
+  return secp_x_is_r(acc, r) && ok;
 }
 
 }  // namespace cmtv

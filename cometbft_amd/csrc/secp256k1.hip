@@ -8,6 +8,12 @@
 //     64 verdicts into one bitmap word.
 //   k_secp_gtab_build: the fixed table (1..128)[256^j]G, one row per thread;
 //     the runtime runs it once per context, on the first secp256k1 batch.
+//   k_secp_qcomb_build: the same table for each registered key Q,
+//     (1..128)[256^j]Q, one thread per (key, j); run by
+//     cmtv_register_keys_secp256k1.
+//   k_verify_secp256k1_keyed: one signature per lane by registered key
+//     (secp_verify_keyed_one): both scalar multiplications are combs, 33
+//     additions from the fixed table and 33 from the key's; no scratch.
 //
 // Memory layout: pk n x 33 B and sig n x 64 B (read bytewise: a 33-byte
 // stride has no alignment), msg flat bytes + (n+1) u32 offsets as the other
@@ -101,6 +107,66 @@ __global__ __launch_bounds__(64, 2) void k_verify_secp256k1(uint32_t n, const ui
   if (active && out_valid) out_valid[gid] = v ? 1 : 0;
   const uint64_t mask = __ballot(v);
   if (threadIdx.x == 0 && out_bitmap) out_bitmap[gid >> 6] = mask;
+}
+
+// One thread per (key, position): position-major, so that a wave's lanes
+// (nearly always) share j and with it the doubling loop's trip count. The
+// thread's 128 rows go straight to the table (16 KiB per thread, written once).
+__global__ __launch_bounds__(64) void k_secp_qcomb_build(uint32_t n_keys, const uint8_t* __restrict__ pk,
+                                                         uint8_t* __restrict__ ok, uint32_t* __restrict__ tab) {
+  const uint32_t gid = blockIdx.x * 64 + threadIdx.x;
+  if (gid >= n_keys * (uint32_t)SECP_GTAB_POS) return;
+  const uint32_t j = gid / n_keys, key = gid % n_keys;
+  uint32_t* rows = tab + (size_t)key * kSecpGtabWords + (size_t)j * (SECP_GTAB_PER_POS * SECP_GTAB_ROW_WORDS);
+  const bool v = secp_qcomb_position(rows, pk + 33 * (size_t)key, (int)j);
+  if (j == 0) ok[key] = v ? 1 : 0;
+}
+
+// One signature per lane by registered key key_idx[i]: no key bytes, no
+// scratch. An index >= n_keys reads key 0's table and clears the verdict.
+__global__ __launch_bounds__(64) void k_verify_secp256k1_keyed(uint32_t n, uint32_t n_keys,
+                                                               const uint32_t* __restrict__ key_idx,
+                                                               const uint8_t* __restrict__ key_ok,
+                                                               const uint32_t* __restrict__ qtab,
+                                                               const uint8_t* __restrict__ sig,
+                                                               const uint8_t* __restrict__ msg,
+                                                               const uint32_t* __restrict__ off,
+                                                               const uint32_t* __restrict__ gtab,
+                                                               uint8_t* __restrict__ out_valid,
+                                                               uint64_t* __restrict__ out_bitmap) {
+  const uint32_t gid = blockIdx.x * 64 + threadIdx.x;
+  const bool active = gid < n;
+  const uint32_t i = active ? gid : n - 1;
+  const uint32_t m0 = off[i], m1 = off[i + 1];
+  const uint32_t k = key_idx[i];
+  const bool in_set = k < n_keys;
+  const uint32_t key = in_set ? k : 0;
+  DevSecpGTab qt{qtab + (size_t)key * kSecpGtabWords};
+  DevSecpGTab gt{gtab};
+  bool v = secp_verify_keyed_one(in_set && key_ok[key] != 0, sig + 64 * (size_t)i, msg + m0, m1 - m0, qt, gt);
+  v = v && active;
+  if (active && out_valid) out_valid[gid] = v ? 1 : 0;
+  const uint64_t mask = __ballot(v);
+  if (threadIdx.x == 0 && out_bitmap) out_bitmap[gid >> 6] = mask;
+}
+
+hipError_t launch_secp_qcomb_build(uint32_t n_keys, const uint8_t* d_pk, uint8_t* d_ok, uint32_t* d_tab,
+                                   hipStream_t s) {
+  if (n_keys == 0) return hipSuccess;
+  const uint32_t threads = n_keys * (uint32_t)SECP_GTAB_POS;
+  hipLaunchKernelGGL(k_secp_qcomb_build, dim3((threads + 63) / 64), dim3(64), 0, s, n_keys, d_pk, d_ok, d_tab);
+  return hipGetLastError();
+}
+
+hipError_t launch_verify_secp256k1_keyed(uint32_t n, uint32_t n_keys, const uint32_t* key_idx, const uint8_t* key_ok,
+                                         const uint32_t* qtab, const void* sig, const void* msg, const void* off,
+                                         const uint32_t* gtab, void* valid, void* bitmap, hipStream_t s) {
+  if (n == 0) return hipSuccess;
+  hipLaunchKernelGGL(k_verify_secp256k1_keyed, dim3((n + 63) / 64), dim3(64), 0, s, n, n_keys, key_idx, key_ok, qtab,
+                     static_cast<const uint8_t*>(sig), static_cast<const uint8_t*>(msg),
+                     static_cast<const uint32_t*>(off), gtab, static_cast<uint8_t*>(valid),
+                     static_cast<uint64_t*>(bitmap));
+  return hipGetLastError();
 }
 
 hipError_t launch_secp_gtab_build(uint32_t* d_rows, hipStream_t s) {

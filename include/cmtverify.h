@@ -332,6 +332,44 @@ int cmtv_verify_secp256k1(cmtv_ctx* ctx, size_t n, const uint8_t* pk, const uint
 int cmtv_verify_secp256k1_device(cmtv_ctx* ctx, size_t n, const void* d_pk, const void* d_sig, const void* d_msg,
                                  const void* d_msg_off, void* d_valid, void* d_bitmap, void* stream);
 
+/* Registered secp256k1 keys: the same call site (crypto/secp256k1/
+ * secp256k1.go:192-217) for a validator set that signs commit after commit
+ * with the same keys. cmtv_register_keys_secp256k1 parses n_keys 33-byte
+ * compressed keys once (pk is n_keys x 33 bytes, 1 <= n_keys <= 65,536) and
+ * builds, per key Q, the radix-256 comb d*256^j*Q (j <= 32, 1 <= d <= 128;
+ * 528 KiB of HBM per key), so that indexed verification needs no
+ * decompression of Q, no per-signature table and no doublings: 33 table
+ * additions for [e/s]G and 33 for [r/s]Q. Verdicts are identical to
+ * cmtv_verify_secp256k1's on the same (pk, msg, sig): registration succeeds
+ * for a key that verification would reject (prefix not 2 or 3, x >= p, not on
+ * the curve), and every signature under that key is invalid. The tables live
+ * on the context's first device only, where every secp256k1 batch runs
+ * (CMTV_ENODEV once it is retired); the verdict cache and the keyset cache do
+ * not apply. Blocking. The key set belongs to `ctx`: free it before
+ * cmtv_close(ctx). cmtv_secp_keyset_free(NULL) is a no-op and
+ * cmtv_secp_keyset_len(NULL) is 0. */
+typedef struct cmtv_secp_keyset cmtv_secp_keyset;
+int cmtv_register_keys_secp256k1(cmtv_ctx* ctx, size_t n_keys, const uint8_t* pk, cmtv_secp_keyset** out);
+void cmtv_secp_keyset_free(cmtv_secp_keyset* ks);
+size_t cmtv_secp_keyset_len(const cmtv_secp_keyset* ks);
+
+/* Verification of n signatures where signature i is by registered key
+ * key_idx[i] (every index must be < cmtv_secp_keyset_len: CMTV_EINVAL
+ * otherwise, before anything is copied or launched). Buffers and outputs as
+ * in cmtv_verify_secp256k1; launches of at most CMTV_LANE_CHUNK signatures,
+ * no scratch. Blocking. */
+int cmtv_verify_secp256k1_indexed(cmtv_ctx* ctx, const cmtv_secp_keyset* ks, size_t n, const uint32_t* key_idx,
+                                  const uint8_t* sig, const uint8_t* msg, const uint32_t* msg_off,
+                                  uint8_t* out_valid, uint64_t* out_bitmap);
+
+/* Same with device-resident inputs, enqueued on `stream` (NULL = HIP null
+ * stream), non-blocking; d_valid and d_bitmap are each optional. An
+ * out-of-range d_key_idx entry gives an invalid verdict (the kernel never
+ * reads outside the key set). */
+int cmtv_verify_secp256k1_indexed_device(cmtv_ctx* ctx, const cmtv_secp_keyset* ks, size_t n, const void* d_key_idx,
+                                         const void* d_sig, const void* d_msg, const void* d_msg_off, void* d_valid,
+                                         void* d_bitmap, void* stream);
+
 /* ------------------------------------------------------------ registered keys */
 
 /* A validator set signs commit after commit with the same keys (blocksync,
