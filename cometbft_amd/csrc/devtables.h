@@ -1,5 +1,5 @@
 // devtables.h -- device-side table policies shared by the gfx950 kernels
-// (kernels.hip, sr25519.hip): the fixed-base B table and the per-lane
+// (kernels.hip, keyed_forms.hip, keygen.hip, sr25519.hip): the fixed-base B table and the per-lane
 // (1..8)(-A) table of the one-signature-per-lane Straus (verify_core.h), and
 // the quad kernels' B-table, DPP quad and LDS table policies (quad.h).
 #pragma once

@@ -481,12 +481,10 @@ CMTV_HD void hs_digits16(uint32_t t[8], const uint32_t x[8], int W) {
   }
 }
 
-// Signed radix-2^16 digit streams of u < L (< 2^253): t = u + 0x8000 in every
-// 16-bit field (the top field stays below 2^16), tLo yields digits 7..0
-// (bits 0..127) and tHi digits 15..8, each read from the top with
-// sc_shift_out(t, 16); digit = out - 0x8000, in [-2^15, 2^15).
-CMTV_HD void hs_digits65536(uint32_t tLo[8], uint32_t tHi[8], const uint32_t u[8]) {
-  uint32_t t[8];
+// t = u + 0x8000 in every 16-bit field, for u < L (< 2^253: the top field
+// stays below 2^16): field j of t, less 0x8000, is the signed radix-2^16 digit
+// j of u, in [-2^15, 2^15).
+CMTV_HD void hs_recode65536(uint32_t t[8], const uint32_t u[8]) {
   uint64_t c = 0;
 #pragma unroll
   for (int i = 0; i < 8; i++) {
@@ -494,6 +492,14 @@ CMTV_HD void hs_digits65536(uint32_t tLo[8], uint32_t tHi[8], const uint32_t u[8
     t[i] = (uint32_t)v;
     c = v >> 32;
   }
+}
+
+// Signed radix-2^16 digit streams of u < L: of t = hs_recode65536(u), tLo
+// yields digits 7..0 (bits 0..127) and tHi digits 15..8, each read from the
+// top with sc_shift_out(t, 16); digit = out - 0x8000.
+CMTV_HD void hs_digits65536(uint32_t tLo[8], uint32_t tHi[8], const uint32_t u[8]) {
+  uint32_t t[8];
+  hs_recode65536(t, u);
 #pragma unroll
   for (int i = 0; i < 4; i++) {
     tLo[i] = 0;

@@ -1,4 +1,6 @@
-// kernels.h -- host-side launchers for the gfx950 kernels (kernels.hip).
+// kernels.h -- host-side launchers for the gfx950 kernels (kernels.hip,
+// keyed_forms.hip, keyed_lane.hip, keygen.hip, sr25519.hip, secp256k1.hip,
+// signbytes.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -36,7 +38,7 @@ constexpr uint32_t kKeyedRow = 0, kKeyedQuad = 1, kKeyedLane = 2;
 
 // Row kernel bitmap assembly: each launch takes the next of kRowSlots slots
 // of a per-device ring (kRowSlotWords words, read as 64-bit words of 32
-// two-bit verdict fields: kernels.hip row_bitmap_add); the wave that fills a
+// two-bit verdict fields: kernel_parts.h row_bitmap_add); the wave that fills a
 // word's last field writes that word's 32 bitmap bits and zeroes it. A slot is
 // reused after kRowSlots further row launches on the device; the runtime
 // fences a reuse against the slot's previous launch (launch.cpp

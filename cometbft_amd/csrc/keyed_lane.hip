@@ -19,6 +19,7 @@
 #include <hip/hip_runtime.h>
 
 #include "devtables.h"
+#include "kernel_parts.h"
 #include "kernels.h"
 #include "keyed.h"
 
@@ -268,10 +269,7 @@ __global__ __launch_bounds__(64, CMTV_KEYED_WAVES_PER_EU) void k_verify_keyed(
   const bool ok = keyed_comb_dev<COMB>(acc, kid, kin && keys_ok[kid] != 0, keys_pk, sig + 16 * (size_t)i, msg + m0,
                                        m1 - m0, ktabs, btab, stage_);
   bool v = check_R<MODE>(acc, sig + 16 * (size_t)i) && ok;
-  v = v && active;
-  if (active && out_valid) out_valid[gid] = v ? 1 : 0;
-  const uint64_t mask = __ballot(v);
-  if (threadIdx.x == 0 && out_bitmap) out_bitmap[gid >> 6] = mask;
+  lane_verdict_store(gid, active, v, out_valid, out_bitmap);
 }
 
 // Registered-key verification with KB signatures per lane sharing one field

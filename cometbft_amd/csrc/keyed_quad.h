@@ -58,7 +58,7 @@ struct NoBTabQ {
 // additions need only s, so they run first; get_k(tk) is called before the
 // 32 key-comb additions and get_r(rc, r_ok) (this lane's coordinate of R: x,
 // y, 1, t) before the final check -- a helper wave hashes and decodes
-// meanwhile (kernels.hip k_verify_keyed_quad_split). [s]B: B16 = over the B
+// meanwhile (keyed_forms.hip k_verify_keyed_quad_split). [s]B: B16 = over the B
 // table's radix-2^16 comb (bt.load_coord(row, off, fe&): BC16 rows, 16
 // additions), else over the radix-256 comb bcomb (32).
 template <uint32_t MODE, bool B16 = false, class Q, class BT = NoBTabQ, class GetK, class GetR>

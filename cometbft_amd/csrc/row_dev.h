@@ -1,5 +1,5 @@
 // row_dev.h -- the device row policy and LDS table policy of the
-// one-signature-per-wave verifier (row.h; k_verify_row_split in kernels.hip,
+// one-signature-per-wave verifier (row.h; the row kernels of kernels.hip and keyed_forms.hip,
 // tools/microbench/row_lat.hip).
 #pragma once
 #include <hip/hip_runtime.h>

@@ -24,6 +24,7 @@
 // 32 words (16-byte aligned): a lane gathers its row with dwordx4 loads.
 #include <hip/hip_runtime.h>
 
+#include "kernel_parts.h"
 #include "kernels.h"
 #include "secp256k1.h"
 
@@ -103,10 +104,7 @@ __global__ __launch_bounds__(64, 2) void k_verify_secp256k1(uint32_t n, const ui
   DevSecpQTab qt{qtab, gridDim.x * 64u, gid};
   DevSecpGTab gt{gtab};
   bool v = secp_verify_one(pk + 33 * (size_t)i, sig + 64 * (size_t)i, msg + m0, m1 - m0, qt, gt);
-  v = v && active;
-  if (active && out_valid) out_valid[gid] = v ? 1 : 0;
-  const uint64_t mask = __ballot(v);
-  if (threadIdx.x == 0 && out_bitmap) out_bitmap[gid >> 6] = mask;
+  lane_verdict_store(gid, active, v, out_valid, out_bitmap);
 }
 
 // One thread per (key, position): position-major, so that a wave's lanes
@@ -144,10 +142,7 @@ __global__ __launch_bounds__(64) void k_verify_secp256k1_keyed(uint32_t n, uint3
   DevSecpGTab qt{qtab + (size_t)key * kSecpGtabWords};
   DevSecpGTab gt{gtab};
   bool v = secp_verify_keyed_one(in_set && key_ok[key] != 0, sig + 64 * (size_t)i, msg + m0, m1 - m0, qt, gt);
-  v = v && active;
-  if (active && out_valid) out_valid[gid] = v ? 1 : 0;
-  const uint64_t mask = __ballot(v);
-  if (threadIdx.x == 0 && out_bitmap) out_bitmap[gid >> 6] = mask;
+  lane_verdict_store(gid, active, v, out_valid, out_bitmap);
 }
 
 hipError_t launch_secp_qcomb_build(uint32_t n_keys, const uint8_t* d_pk, uint8_t* d_ok, uint32_t* d_tab,

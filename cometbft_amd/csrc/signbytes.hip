@@ -10,17 +10,9 @@
 
 namespace cmtv {
 
+// Byte writer (signbytes.h sb_write) to the output, or to the block's LDS image of it
 struct DevBytes {
   uint8_t* __restrict__ p;
-  __device__ __forceinline__ void put(uint32_t pos, uint8_t b) { p[pos] = b; }
-  __device__ __forceinline__ void copy(uint32_t pos, const uint8_t* src, uint32_t len) {
-    for (uint32_t i = 0; i < len; i++) p[pos + i] = src[i];
-  }
-};
-
-// The same writer into the block's LDS image
-struct LdsBytes {
-  uint8_t* p;
   __device__ __forceinline__ void put(uint32_t pos, uint8_t b) { p[pos] = b; }
   __device__ __forceinline__ void copy(uint32_t pos, const uint8_t* src, uint32_t len) {
     for (uint32_t i = 0; i < len; i++) p[pos + i] = src[i];
@@ -65,7 +57,7 @@ __global__ __launch_bounds__(256) void k_sign_bytes(uint32_t n, const SbTemplate
   }
   if (i < n) {
     const SbTemplate t = tmpls[tidx[i]];
-    LdsBytes out{img + lo + (off[i] - start)};
+    DevBytes out{img + lo + (off[i] - start)};
     sb_write(out, t, blob, commit_flag[i] != 0, sec[i], nanos[i]);
   }
   __syncthreads();

@@ -6,7 +6,7 @@ its bitmap through one slot of a 256-slot per-device ring: slot word j holds
 the 2-bit verdict fields (01 rejected, 10 accepted) of signatures 32j..32j+31,
 each added by its signature's wave with one atomic, and the wave whose add
 fills the word's last field writes the word's 32 bitmap bits and zeroes it
-(kernels.hip row_bitmap_add). Two launches sharing a slot would add into the
+(kernel_parts.h row_bitmap_add). Two launches sharing a slot would add into the
 same fields: two rejects sum to the accept pattern. Device-resident calls
 (cmtv_verify_ed25519_device and friends) are non-blocking on the caller's
 streams, so a caller can have a launch parked behind other work while 256

@@ -5,7 +5,7 @@ of the library (where its 71 us go).
   make -C cometbft_amd/csrc OUT=../../tools/probe/libprobe.so BUILD=../../build/probe KFLAGS=-DCMTV_PHASE_PROBE
   CMTV_LIBRARY=$PWD/tools/probe/libprobe.so python tools/keyed_phase.py [n]
 
-Five waves per workgroup (kernels.hip CMTV_STAMP5): 0 entry; the hash
+Five waves per workgroup (keyed_forms.hip, phase_probe.h CMTV_STAMP5): 0 entry; the hash
 helper (wave 4) slot 3 = k published; the decode helper (wave 3) slot 3 = R
 decoded; the quads (waves 0-2) slot 4 = k taken, 1 = their 48 comb additions
 done (before the barrier), 2 = after it, 5 = exit. Cycles of the shader clock
@@ -34,7 +34,7 @@ def main():
     from cometbft_amd import testutil as TU
 
     L = N.lib()
-    L.cmtv_debug_phase_times.argtypes = [ctypes.POINTER(ctypes.c_uint64), ctypes.c_size_t]
+    L.cmtv_debug_phase_times_keyed.argtypes = [ctypes.POINTER(ctypes.c_uint64), ctypes.c_size_t]
     ctx = Context(device=0)
     m, off = pack_messages(TU.commit_messages(n, 1000))
     sv = TU.make_validator_set(ctx, n)
@@ -58,7 +58,7 @@ def main():
         torch.cuda.synchronize()
         assert d_valid.cpu().numpy().all()
         buf = np.zeros(wgs * 5 * SLOTS, np.uint64)
-        assert L.cmtv_debug_phase_times(buf.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)), buf.size) == 0
+        assert L.cmtv_debug_phase_times_keyed(buf.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)), buf.size) == 0
         st = buf.reshape(wgs, 5, SLOTS).astype(np.int64)
         simd = (st[:, :, 6] >> 4) & 3  # HW_ID of each wave: its SIMD
         shares = {f"wave{w}": int((simd[:, w][:, None] == np.delete(simd, w, axis=1)).any(axis=1).sum())

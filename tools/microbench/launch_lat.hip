@@ -132,7 +132,7 @@ __global__ __launch_bounds__(256, 1) void k_spin_ticket(uint64_t ticks, uint64_t
   if (tl == 0) __hip_atomic_store(slot, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
-// the spin, then kernels.hip row_bitmap_add's epilogue: one relaxed 64-bit
+// the spin, then kernel_parts.h row_bitmap_add's epilogue: one relaxed 64-bit
 // atomic add of a 2-bit verdict field per wave; the wave that fills a word's
 // last field packs it with a ballot (no fence, no serial byte loop)
 __global__ __launch_bounds__(256, 1) void k_spin_fields(uint64_t ticks, uint64_t* stamps, uint32_t* slot,

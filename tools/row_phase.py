@@ -5,7 +5,7 @@ library.
   make -C cometbft_amd/csrc OUT=../../abtest/libprobe.so BUILD=../../build/probe KFLAGS=-DCMTV_PHASE_PROBE
   CMTV_LIBRARY=$PWD/abtest/libprobe.so python tools/row_phase.py [n] [row4|krow]
 
-Shader-clock stamps per wave (kernels.hip CMTV_STAMP), relative to the
+Shader-clock stamps per wave (phase_probe.h CMTV_STAMP), relative to the
 workgroup's first entry: row4's lo wave (0): 1/2 at/after barrier 1, 3/4
 at/after barrier 2, 5 verdict; A-hi and R-hi (1, 2): 6 decoded, 1-3 as lo;
 helper (3): 1 scalars ready, 3 [u]B ready. Medians over workgroups, per mode, into gpurun_out/row_phase.json.
@@ -29,7 +29,8 @@ def main():
     from cometbft_amd import _native as N
     from cometbft_amd import testutil as TU
 
-    fn = N.lib().cmtv_debug_phase_times
+    # each kernel file has its own stamp buffer: the keyed row kernel is in keyed_forms.hip
+    fn = N.lib().cmtv_debug_phase_times_keyed if form == "krow" else N.lib().cmtv_debug_phase_times
     fn.argtypes = [ctypes.POINTER(ctypes.c_uint64), ctypes.c_size_t]
     ctx = Context(device=0)
     sv = TU.make_validator_set(ctx, n)
@@ -64,7 +65,7 @@ def main():
         res["launch_span"] = float(st[:, 0, 5].max() - t0.min())
         res["end_median"] = float(np.median(st[:, 0, 5] - t0))
         if form == "row4":
-            # the 100 MHz constant clock (kernels.hip CMTV_STAMP_RT): entry of
+            # the 100 MHz constant clock (phase_probe.h CMTV_STAMP_RT): entry of
             # every wave (slot 7) and the lo wave's verdict (slot 6)
             rt0 = st[:, :nw, 7].min(axis=1)
             cyc = (st[:, 0, 5] - t0).astype(np.float64)
