@@ -27,6 +27,12 @@ VERIFY_COMMIT = 0
 VERIFY_COMMIT_LIGHT = 1
 VERIFY_COMMIT_LIGHT_TRUSTING = 2
 
+# cmtv_verify_commit_typed key types
+KEY_ED25519 = 0
+KEY_SECP256K1 = 1
+KEY_SR25519 = 2
+KEY_TYPES = {"ed25519": KEY_ED25519, "secp256k1": KEY_SECP256K1, "sr25519": KEY_SR25519}
+
 COMMIT_OK = 0
 COMMIT_ERR_SET_SIZE = 1
 COMMIT_ERR_HEIGHT = 2
@@ -50,7 +56,7 @@ EXPORTS = (
     "cmtv_register_keys", "cmtv_register_keys_ex", "cmtv_keyset_free", "cmtv_keyset_len", "cmtv_verify_ed25519_indexed",
     "cmtv_verify_ed25519_indexed_device",
     "cmtv_batch_new", "cmtv_batch_add", "cmtv_batch_len", "cmtv_batch_verify", "cmtv_batch_reset",
-    "cmtv_batch_free", "cmtv_verify_commit", "cmtv_verify_commits", "cmtv_verdict_cache", "cmtv_keyset_cache", "cmtv_vote_sign_bytes", "cmtv_pubkeys_ed25519", "cmtv_sign_ed25519",
+    "cmtv_batch_free", "cmtv_verify_commit", "cmtv_verify_commit_typed", "cmtv_verify_commits", "cmtv_verdict_cache", "cmtv_keyset_cache", "cmtv_vote_sign_bytes", "cmtv_pubkeys_ed25519", "cmtv_sign_ed25519",
     "cmtv_alloc_pinned", "cmtv_free_pinned",
 )
 
@@ -209,6 +215,10 @@ def lib() -> ctypes.CDLL:
                                      ctypes.POINTER(cmtv_block_id), i64, ctypes.POINTER(cmtv_commit), u64, u64,
                                      ctypes.POINTER(cmtv_commit_result), ctypes.c_char_p, sz]
     L.cmtv_verify_commit.restype = ctypes.c_int
+    L.cmtv_verify_commit_typed.argtypes = [vp, u32, u32, ctypes.c_char_p, sz, ctypes.POINTER(cmtv_valset), _u8p,
+                                           ctypes.POINTER(cmtv_block_id), i64, ctypes.POINTER(cmtv_commit), u64, u64,
+                                           ctypes.POINTER(cmtv_commit_result), ctypes.c_char_p, sz]
+    L.cmtv_verify_commit_typed.restype = ctypes.c_int
     L.cmtv_verify_commits.argtypes = [vp, u32, u32, ctypes.c_char_p, sz, sz, ctypes.POINTER(cmtv_valset),
                                       ctypes.POINTER(cmtv_block_id), ctypes.POINTER(i64), ctypes.POINTER(cmtv_commit),
                                       u64, u64, ctypes.POINTER(cmtv_commit_result), ctypes.POINTER(ctypes.c_int),

@@ -464,7 +464,9 @@ size_t job_plan(const CommitJob& J, uint32_t* pidx, uint32_t* pval, Seen& seen) 
         seen.put(vi, idx);
       }
     }
-    if (vals->pk_off[vi + 1] - vals->pk_off[vi] != 32) break;  // panics here
+    // panics here (an Ed25519 key only: the other types' VerifySignature
+    // returns false for a key it cannot use, a verdict like any other)
+    if (J.key_type(vi) == CMTV_KEY_ED25519 && vals->pk_off[vi + 1] - vals->pk_off[vi] != 32) break;
     pidx[m] = idx;
     if (pval) pval[m] = vi;
     m++;

@@ -288,7 +288,11 @@ struct CommitJob {
   // (the pipeline: one sum per distinct set, not per commit)
   bool has_total = false;
   int64_t total = 0;
+  // typed validator sets (commit_typed.cpp): one CMTV_KEY_* per validator;
+  // null = every key is Ed25519, and nothing below changes
+  const uint8_t* key_types = nullptr;
 
+  uint8_t key_type(uint32_t vi) const { return key_types ? key_types[vi] : (uint8_t)CMTV_KEY_ED25519; }
   int fail(int32_t code, int32_t idx, const std::string& m) {
     res->code = code;
     res->sig_index = idx;
@@ -344,7 +348,9 @@ size_t job_plan(const CommitJob& J, uint32_t* pidx, uint32_t* pval, Seen& seen);
 // the commit's first m signatures): valid(j) is plan item j's
 // device verdict; a signature whose length is not 64 is invalid whatever the
 // device said, and fails before its key's length is looked at
-// (crypto/ed25519/ed25519.go:150).
+// (crypto/ed25519/ed25519.go:150). With J.key_types only an Ed25519 key's
+// length can panic: a secp256k1 or sr25519 key of any length gives a verdict
+// (crypto/secp256k1/secp256k1.go:192-200, crypto/sr25519/pubkey.go:36-45).
 template <class V>
 int job_replay(CommitJob& J, const uint32_t* pidx, size_t m, V valid, Seen& seen) {
   if (J.early != 1) return J.early;
@@ -371,7 +377,8 @@ int job_replay(CommitJob& J, const uint32_t* pidx, size_t m, V valid, Seen& seen
       if (flag != kFlagCommit && flag != kFlagNil)
         return J.fail(CMTV_COMMIT_PANIC_UNKNOWN_FLAG, (int32_t)idx, "Unknown BlockIDFlag: " + std::to_string(flag));
       if (!sig64(idx)) return wrong_sig(idx);
-      if (vals->pk_off[idx + 1] - vals->pk_off[idx] != 32) return bad_pk(idx, idx);
+      if (J.key_type(idx) == CMTV_KEY_ED25519 && vals->pk_off[idx + 1] - vals->pk_off[idx] != 32)
+        return bad_pk(idx, idx);
       if (j >= m || (pidx ? pidx[j] : (uint32_t)j) != idx || !valid(j)) return wrong_sig(idx);
       j++;
       if (flag == kFlagCommit) tally += vals->voting_power[idx];
@@ -385,7 +392,11 @@ int job_replay(CommitJob& J, const uint32_t* pidx, size_t m, V valid, Seen& seen
         uint32_t first = 0;
         if (seen.has(vi, &first)) {
           // Validator.String(): "Validator{%v %v VP:%v A:%v}" (types/validator.go)
-          std::string vs = "Validator{" + hex_upper(vals->addrs + 20 * (size_t)vi, 20) + " PubKeyEd25519{" +
+          const uint8_t kt = J.key_type(vi);
+          std::string vs = "Validator{" + hex_upper(vals->addrs + 20 * (size_t)vi, 20) +
+                           (kt == CMTV_KEY_SECP256K1 ? " PubKeySecp256k1{"
+                            : kt == CMTV_KEY_SR25519 ? " PubKeySr25519{"
+                                                     : " PubKeyEd25519{") +
                            hex_upper(vals->pubkeys + vals->pk_off[vi], vals->pk_off[vi + 1] - vals->pk_off[vi]) +
                            "} VP:" + std::to_string(vals->voting_power[vi]) + " A:" +
                            std::to_string(vals->proposer_priority ? vals->proposer_priority[vi] : 0) + "}";
@@ -400,7 +411,8 @@ int job_replay(CommitJob& J, const uint32_t* pidx, size_t m, V valid, Seen& seen
         seen.put(vi, idx);
       }
       if (!sig64(idx)) return wrong_sig(idx);
-      if (vals->pk_off[vi + 1] - vals->pk_off[vi] != 32) return bad_pk(idx, vi);
+      if (J.key_type(vi) == CMTV_KEY_ED25519 && vals->pk_off[vi + 1] - vals->pk_off[vi] != 32)
+        return bad_pk(idx, vi);
       if (j >= m || (pidx ? pidx[j] : (uint32_t)j) != idx || !valid(j)) return wrong_sig(idx);
       j++;
       tally += vals->voting_power[vi];

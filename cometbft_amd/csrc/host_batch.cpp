@@ -1,7 +1,8 @@
 // host_batch.cpp -- batches in host memory: staging and launch of a shard
 // (enqueue_shard), the single-device mapped-memory call and the sharded one
 // (run_host_batch), the verdict cache in front of them, templated commit
-// batches, early-staged signatures and the secp256k1 host call.
+// batches, early-staged signatures and the secp256k1 host calls (messages in
+// host memory, or commit signatures with templated sign-bytes).
 #include <functional>
 
 #include "runtime_state.h"
@@ -737,6 +738,97 @@ int verify_secp_keyed_host_locked(cmtv_ctx* ctx, const cmtv_secp_keyset* ks, siz
   if ((e = hipMemcpyAsync(bm.data(), dbm, 8 * words, hipMemcpyDeviceToHost, s)) != hipSuccess) return hip_fail(e);
   if ((e = wait_stream(ctx, s)) != hipSuccess) return hip_fail(e);
   ctx->stats.invalid += bitmap_tail(bm.data(), n, out_bitmap, out_valid);
+  return CMTV_OK;
+}
+
+// Commit signatures over secp256k1 keys with templated sign-bytes
+// (runtime_internal.h): one staging block
+//   sec i64 | nanos i32 | tidx u32 | key_idx u32 (registered keys) | off u32
+//   (n + 1, non-fused only) | templates | sig | pk (n x 33) | flag | blob
+// with the 8-byte array first and the 4-byte ones next, so every array the
+// kernels read as int64 / int32 is aligned whatever n is; on the device the
+// non-fused route's messages follow it.
+int verify_secp_templated_locked(cmtv_ctx* ctx, size_t n, const uint8_t* pk33, const cmtv_secp_keyset* ks,
+                                 const uint32_t* key_idx, const uint8_t* sig, const void* tmpls, size_t n_tmpls,
+                                 const uint8_t* blob, size_t blob_len, const uint32_t* tidx,
+                                 const uint8_t* commit_flag, const int64_t* sec, const int32_t* nanos,
+                                 uint8_t* out_valid) {
+  if (n == 0) return CMTV_OK;
+  if (!sig || !tmpls || !n_tmpls || !commit_flag || !sec || !nanos || (ks ? !key_idx : !pk33)) return CMTV_EINVAL;
+  if (ctx->devs.empty() || ctx->devs[0].failed) return CMTV_ENODEV;
+  CmtvDev& D = ctx->devs[0];
+  (void)hipSetDevice(D.ordinal);
+  const auto* tp = static_cast<const SbTemplate*>(tmpls);
+  // message lengths: they decide the route, and give the non-fused route's offsets
+  uint32_t max_len = 0;
+  uint64_t total = 0;
+  for (size_t i = 0; i < n; i++) {
+    const uint32_t ti = tidx ? tidx[i] : 0u;
+    if (ti >= n_tmpls) return CMTV_EINVAL;
+    if (ks && key_idx[i] >= ks->n) return CMTV_EINVAL;
+    const uint32_t len = sb_msg_len(tp[ti], commit_flag[i] != 0, sec[i], nanos[i]);
+    max_len = std::max(max_len, len);
+    total += len;
+  }
+  if (total + 16 >= (1ull << 31)) return CMTV_EINVAL;
+  const bool fuse = ctx->sb_fuse && max_len <= kSbFuseMaxMsg;
+  static_assert(sizeof(SbTemplate) % 4 == 0, "the arrays after the templates stay 4-byte aligned");
+  const size_t tb = n_tmpls * sizeof(SbTemplate);
+  const size_t o_sec = 0, o_nanos = o_sec + 8 * n, o_tidx = o_nanos + 4 * n, o_kidx = o_tidx + 4 * n;
+  const size_t o_off = o_kidx + (ks ? 4 * n : 0), o_tmpl = o_off + (fuse ? 0 : 4 * (n + 1));
+  const size_t o_sig = o_tmpl + tb, o_pk = o_sig + 64 * n, o_flag = o_pk + (ks ? 0 : 33 * n), o_blob = o_flag + n;
+  // +16: the template runs are fetched in aligned words (LdsBytes::copy)
+  const size_t in_bytes = align_up(o_blob + blob_len + 16, 16);
+  // k_sign_bytes writes 16 zero bytes after the last message
+  const size_t o_msg = in_bytes, dev_bytes = fuse ? in_bytes : align_up(o_msg + total + 16 + 4, 16);
+  const size_t words = (n + 63) / 64;
+  hipError_t e;
+  if ((e = D.secp_in.ensure(dev_bytes)) != hipSuccess) return hip_fail(e);
+  if ((e = D.secp_out.ensure(8 * words)) != hipSuccess) return hip_fail(e);
+  if (D.secp_stage.size() < in_bytes) D.secp_stage.resize(in_bytes);
+  uint8_t* h = D.secp_stage.data();
+  std::memcpy(h + o_sec, sec, 8 * n);
+  std::memcpy(h + o_nanos, nanos, 4 * n);
+  if (tidx)
+    std::memcpy(h + o_tidx, tidx, 4 * n);
+  else
+    std::memset(h + o_tidx, 0, 4 * n);
+  if (ks) std::memcpy(h + o_kidx, key_idx, 4 * n);
+  if (!fuse) {
+    uint32_t o = 0;
+    for (size_t i = 0; i <= n; i++) {
+      std::memcpy(h + o_off + 4 * i, &o, 4);
+      if (i < n) o += sb_msg_len(tp[tidx ? tidx[i] : 0u], commit_flag[i] != 0, sec[i], nanos[i]);
+    }
+  }
+  std::memcpy(h + o_tmpl, tmpls, tb);
+  std::memcpy(h + o_sig, sig, 64 * n);
+  if (!ks) std::memcpy(h + o_pk, pk33, 33 * n);
+  std::memcpy(h + o_flag, commit_flag, n);
+  if (blob_len) std::memcpy(h + o_blob, blob, blob_len);
+  std::memset(h + o_blob + blob_len, 0, in_bytes - o_blob - blob_len);
+  auto* din = static_cast<uint8_t*>(D.secp_in.p);
+  hipStream_t s = D.stream;
+  if ((e = hipMemcpyAsync(din, h, in_bytes, hipMemcpyHostToDevice, s)) != hipSuccess) return hip_fail(e);
+  SbFuse sb;
+  sb.tmpls = din + o_tmpl;
+  sb.blob = din + o_blob;
+  sb.tidx = reinterpret_cast<const uint32_t*>(din + o_tidx);
+  sb.flag = din + o_flag;
+  sb.sec = reinterpret_cast<const int64_t*>(din + o_sec);
+  sb.nanos = reinterpret_cast<const int32_t*>(din + o_nanos);
+  auto* dbm = static_cast<uint64_t*>(D.secp_out.p);
+  const int rc = enqueue_verify_secp_templated(ctx, D, n, din + o_pk, ks, reinterpret_cast<const uint32_t*>(din + o_kidx),
+                                               din + o_sig, sb, max_len, reinterpret_cast<const uint32_t*>(din + o_off),
+                                               din + o_msg, nullptr, dbm, s);
+  if (rc != CMTV_OK) {
+    (void)hipStreamSynchronize(s);  // the copy reads the staging
+    return rc;
+  }
+  std::vector<uint64_t> bm(words);
+  if ((e = hipMemcpyAsync(bm.data(), dbm, 8 * words, hipMemcpyDeviceToHost, s)) != hipSuccess) return hip_fail(e);
+  if ((e = wait_stream(ctx, s)) != hipSuccess) return hip_fail(e);
+  ctx->stats.invalid += bitmap_tail(bm.data(), n, nullptr, out_valid);
   return CMTV_OK;
 }
 

@@ -59,7 +59,8 @@ struct RowSlot {
 };
 
 // Templated sign-bytes (signbytes.h) written by the helper waves of the
-// helper-wave kernels themselves (every form but the lane kernels): each
+// helper-wave kernels themselves (every Ed25519 form but the lane kernels;
+// the secp256k1 templated kernels, where every lane is its own helper): each
 // helper lane builds its signature's CanonicalVote into an LDS slot of
 // kSbFuseMaxMsg bytes and hashes it from there, so a templated commit needs
 // no k_sign_bytes launch (and no global message buffer). Device pointers;
@@ -140,6 +141,16 @@ hipError_t launch_secp_qcomb_build(uint32_t n_keys, const uint8_t* d_pk, uint8_t
 hipError_t launch_verify_secp256k1_keyed(uint32_t n, uint32_t n_keys, const uint32_t* key_idx, const uint8_t* key_ok,
                                          const uint32_t* qtab, const void* sig, const void* msg, const void* off,
                                          const uint32_t* gtab, void* valid, void* bitmap, hipStream_t s);
+// the two with each lane's message built by the lane from its commit's
+// template (sb.tmpls set; every message at most kSbFuseMaxMsg bytes; a chunk
+// passes sb with flag / sec / nanos / tidx advanced to its first signature)
+hipError_t launch_verify_secp256k1_tmpl(uint32_t n, const void* pk, const void* sig, const SbFuse& sb,
+                                        const uint32_t* gtab, uint32_t* qtab, void* valid, void* bitmap,
+                                        hipStream_t s);
+hipError_t launch_verify_secp256k1_keyed_tmpl(uint32_t n, uint32_t n_keys, const uint32_t* key_idx,
+                                              const uint8_t* key_ok, const uint32_t* qtab, const void* sig,
+                                              const SbFuse& sb, const uint32_t* gtab, void* valid, void* bitmap,
+                                              hipStream_t s);
 hipError_t launch_sign_bytes(uint32_t n, const void* tmpls, const uint8_t* blob, const uint32_t* tidx,
                              const uint8_t* commit_flag, const int64_t* sec, const int32_t* nanos,
                              const uint32_t* off, uint8_t* msg, hipStream_t s);

@@ -1,7 +1,8 @@
 // keyset.cpp -- registered key sets: the per-device comb (and wide) tables of
 // a validator set, the context's cache of them (cmtv_keyset_cache) with its
 // eviction and pins, and their ABI entry points; and registered secp256k1
-// keys (cmtv_secp_keyset: per-key combs on the first device, no cache).
+// keys (cmtv_secp_keyset: per-key combs on the first device; the typed
+// commits' cache of them).
 #include <new>
 
 #include "runtime_state.h"
@@ -126,6 +127,51 @@ bool keyset_holds_locked(const cmtv_keyset* ks, const uint8_t* pk32, size_t n_ke
 
 bool keyset_cache_enabled(const cmtv_ctx* ctx) { return ctx->keyset_cap != 0; }
 
+// The comb tables of n_keys secp256k1 keys on devs[0] (lock held).
+static int register_secp_keys_locked(cmtv_ctx* ctx, size_t n_keys, const uint8_t* pk, cmtv_secp_keyset** out) {
+  CmtvDev& D = ctx->devs[0];
+  if (D.failed) return CMTV_ENODEV;
+  auto* ks = new (std::nothrow) cmtv_secp_keyset();
+  if (!ks) return CMTV_ENOMEM;
+  ks->ctx = ctx;
+  ks->n = n_keys;
+  ks->pk.assign(pk, pk + 33 * n_keys);
+  (void)hipSetDevice(D.ordinal);
+  hipError_t e = hipMalloc(&ks->d_pk, 33 * n_keys);
+  if (e == hipSuccess) e = hipMalloc(&ks->d_ok, n_keys);
+  if (e == hipSuccess) e = hipMalloc(&ks->d_tab, n_keys * (size_t)kSecpGtabWords * sizeof(uint32_t));
+  if (e == hipSuccess) e = hipMemcpyAsync(ks->d_pk, pk, 33 * n_keys, hipMemcpyHostToDevice, D.stream);
+  if (e == hipSuccess) e = launch_secp_qcomb_build((uint32_t)n_keys, ks->d_pk, ks->d_ok, ks->d_tab, D.stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(D.stream);
+  if (e != hipSuccess) {
+    (void)hipGetLastError();
+    cmtv_secp_keyset_free(ks);
+    return hip_fail(e);
+  }
+  *out = ks;
+  return CMTV_OK;
+}
+
+// cmtv_keyset_cache's secp256k1 sets (cmtv_ctx::secp_keysets): found by key
+// bytes, registered on first use, the oldest freed when the list is full
+// (every call that used it waited for its verdicts, and cmtv_secp_keyset_free
+// waits for the stream). NULL when the cache is off, the set is too large to
+// register or registration failed.
+const cmtv_secp_keyset* secp_keyset_for_locked(cmtv_ctx* ctx, const uint8_t* pk33, size_t n_keys) {
+  if (!ctx->keyset_cap || n_keys == 0 || n_keys > (1u << 16)) return nullptr;
+  const size_t bytes = 33 * n_keys;
+  for (auto* k : ctx->secp_keysets)
+    if (k->pk.size() == bytes && std::memcmp(k->pk.data(), pk33, bytes) == 0) return k;
+  cmtv_secp_keyset* ks = nullptr;
+  if (register_secp_keys_locked(ctx, n_keys, pk33, &ks) != CMTV_OK) return nullptr;
+  if (ctx->secp_keysets.size() >= ctx->keyset_cap) {
+    cmtv_secp_keyset_free(ctx->secp_keysets.front());
+    ctx->secp_keysets.erase(ctx->secp_keysets.begin());
+  }
+  ctx->secp_keysets.push_back(ks);
+  return ks;
+}
+
 }  // namespace cmtv
 
 using namespace cmtv;
@@ -160,6 +206,10 @@ int cmtv_keyset_cache(cmtv_ctx* ctx, size_t max_sets) {
     evict_keyset_locked(ctx, ctx->keysets.front().second);
     ctx->keysets.erase(ctx->keysets.begin());
   }
+  while (ctx->secp_keysets.size() > max_sets) {
+    cmtv_secp_keyset_free(ctx->secp_keysets.front());
+    ctx->secp_keysets.erase(ctx->secp_keysets.begin());
+  }
   ctx->keyset_cap = max_sets;
   (void)hipSetDevice(ctx->devs[0].ordinal);
   return CMTV_OK;
@@ -190,26 +240,7 @@ int cmtv_register_keys_secp256k1(cmtv_ctx* ctx, size_t n_keys, const uint8_t* pk
   if (!ctx || n_keys == 0 || n_keys > (1u << 16) || !pk) return CMTV_EINVAL;
   std::unique_lock<std::mutex> lk;
   if (ctx_lock(ctx, lk) != CMTV_OK) return CMTV_ENODEV;
-  CmtvDev& D = ctx->devs[0];
-  if (D.failed) return CMTV_ENODEV;
-  auto* ks = new (std::nothrow) cmtv_secp_keyset();
-  if (!ks) return CMTV_ENOMEM;
-  ks->ctx = ctx;
-  ks->n = n_keys;
-  ks->pk.assign(pk, pk + 33 * n_keys);
-  (void)hipSetDevice(D.ordinal);
-  hipError_t e = hipMalloc(&ks->d_pk, 33 * n_keys);
-  if (e == hipSuccess) e = hipMalloc(&ks->d_ok, n_keys);
-  if (e == hipSuccess) e = hipMalloc(&ks->d_tab, n_keys * (size_t)kSecpGtabWords * sizeof(uint32_t));
-  if (e == hipSuccess) e = hipMemcpyAsync(ks->d_pk, pk, 33 * n_keys, hipMemcpyHostToDevice, D.stream);
-  if (e == hipSuccess) e = launch_secp_qcomb_build((uint32_t)n_keys, ks->d_pk, ks->d_ok, ks->d_tab, D.stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(D.stream);
-  if (e != hipSuccess) {
-    cmtv_secp_keyset_free(ks);
-    return hip_fail(e);
-  }
-  *out = ks;
-  return CMTV_OK;
+  return register_secp_keys_locked(ctx, n_keys, pk, out);
 }
 
 void cmtv_secp_keyset_free(cmtv_secp_keyset* ks) {

@@ -221,7 +221,8 @@ int enqueue_verify_keyed(cmtv_ctx* ctx, CmtvDev& D, const cmtv_keyset::PerDev& K
 
 // ---------------------------------------------------------------- secp256k1
 // ECDSA over secp256k1 (secp256k1.hip): one lane kernel for key bytes and one
-// for registered keys, on devs[0] only; no verdict cache, no sharding.
+// for registered keys, each also in a form whose lanes build their messages
+// from commit templates; on devs[0] only; no verdict cache, no sharding.
 
 // The fixed table of G's multiples, built on the device by the context's
 // first secp256k1 batch (cmtv_open's cost and footprint stay as they were).
@@ -241,11 +242,24 @@ static hipError_t ensure_secp_gtab(CmtvDev& D) {
   return hipSuccess;
 }
 
+// A chunk's view of a batch's templated sign-bytes: the per-signature arrays
+// advanced to signature c
+static SbFuse sb_at(const SbFuse& sb, size_t c) {
+  SbFuse r = sb;
+  if (r.tidx) r.tidx += c;
+  r.flag += c;
+  r.sec += c;
+  r.nanos += c;
+  return r;
+}
+
 // Enqueue verification of n secp256k1 signatures whose inputs are in device
-// memory of device D (current on this thread): pk n x 33 bytes.
+// memory of device D (current on this thread): pk n x 33 bytes. With sb the
+// lanes build their messages from the commit templates (d_msg / d_off unused;
+// every message at most kSbFuseMaxMsg bytes).
 int enqueue_verify_secp(cmtv_ctx* ctx, CmtvDev& D, size_t n, const uint8_t* d_pk, const uint8_t* d_sig,
                         const uint8_t* d_msg, const uint32_t* d_off, uint8_t* d_valid, uint64_t* d_bitmap,
-                        hipStream_t s) {
+                        hipStream_t s, const SbFuse* sb) {
   if (n == 0) return CMTV_OK;
   if (fault_hit(ctx) || D.inject_fault) return CMTV_EHIP;
   hipError_t e = ensure_secp_gtab(D);
@@ -259,9 +273,14 @@ int enqueue_verify_secp(cmtv_ctx* ctx, CmtvDev& D, size_t n, const uint8_t* d_pk
   if ((e = L.begin()) != hipSuccess) return hip_fail(e);
   for (size_t c = 0; c < n; c += chunk) {
     const uint32_t cn = (uint32_t)std::min<size_t>(chunk, n - c);
-    e = launch_verify_secp256k1(cn, d_pk + 33 * c, d_sig + 64 * c, d_msg, d_off + c, D.d_secp_gtab,
-                                static_cast<uint32_t*>(S.buf.p), d_valid ? d_valid + c : nullptr,
-                                d_bitmap ? d_bitmap + c / 64 : nullptr, s);
+    if (sb)
+      e = launch_verify_secp256k1_tmpl(cn, d_pk + 33 * c, d_sig + 64 * c, sb_at(*sb, c), D.d_secp_gtab,
+                                       static_cast<uint32_t*>(S.buf.p), d_valid ? d_valid + c : nullptr,
+                                       d_bitmap ? d_bitmap + c / 64 : nullptr, s);
+    else
+      e = launch_verify_secp256k1(cn, d_pk + 33 * c, d_sig + 64 * c, d_msg, d_off + c, D.d_secp_gtab,
+                                  static_cast<uint32_t*>(S.buf.p), d_valid ? d_valid + c : nullptr,
+                                  d_bitmap ? d_bitmap + c / 64 : nullptr, s);
     if ((e = L.launched(e)) != hipSuccess) return hip_fail(e);
   }
   return L.finish(n, &S);
@@ -271,7 +290,7 @@ int enqueue_verify_secp(cmtv_ctx* ctx, CmtvDev& D, size_t n, const uint8_t* d_pk
 // d_idx n key indices in place of the key bytes; no scratch.
 int enqueue_verify_secp_keyed(cmtv_ctx* ctx, CmtvDev& D, const cmtv_secp_keyset* ks, size_t n, const uint32_t* d_idx,
                               const uint8_t* d_sig, const uint8_t* d_msg, const uint32_t* d_off, uint8_t* d_valid,
-                              uint64_t* d_bitmap, hipStream_t s) {
+                              uint64_t* d_bitmap, hipStream_t s, const SbFuse* sb) {
   if (n == 0) return CMTV_OK;
   if (fault_hit(ctx) || D.inject_fault) return CMTV_EHIP;
   hipError_t e = ensure_secp_gtab(D);
@@ -281,13 +300,44 @@ int enqueue_verify_secp_keyed(cmtv_ctx* ctx, CmtvDev& D, const cmtv_secp_keyset*
   const size_t chunk = ctx->lane_chunk;
   for (size_t c = 0; c < n; c += chunk) {
     const uint32_t cn = (uint32_t)std::min<size_t>(chunk, n - c);
-    e = launch_verify_secp256k1_keyed(cn, (uint32_t)ks->n, d_idx + c, ks->d_ok, ks->d_tab, d_sig + 64 * c, d_msg,
-                                      d_off + c, D.d_secp_gtab, d_valid ? d_valid + c : nullptr,
-                                      d_bitmap ? d_bitmap + c / 64 : nullptr, s);
+    if (sb)
+      e = launch_verify_secp256k1_keyed_tmpl(cn, (uint32_t)ks->n, d_idx + c, ks->d_ok, ks->d_tab, d_sig + 64 * c,
+                                             sb_at(*sb, c), D.d_secp_gtab, d_valid ? d_valid + c : nullptr,
+                                             d_bitmap ? d_bitmap + c / 64 : nullptr, s);
+    else
+      e = launch_verify_secp256k1_keyed(cn, (uint32_t)ks->n, d_idx + c, ks->d_ok, ks->d_tab, d_sig + 64 * c, d_msg,
+                                        d_off + c, D.d_secp_gtab, d_valid ? d_valid + c : nullptr,
+                                        d_bitmap ? d_bitmap + c / 64 : nullptr, s);
     if ((e = L.launched(e)) != hipSuccess) return hip_fail(e);
     ctx->stats.keyed_launches++;
   }
   return L.finish(n, nullptr);
+}
+
+// Commit signatures over secp256k1 keys, sign-bytes from the commits'
+// templates: the templated kernels when every message fits a lane's LDS slot
+// (max_len <= kSbFuseMaxMsg); otherwise k_sign_bytes writes the messages to
+// d_msg at the offsets d_off (sb.tidx set then) and the message-reading
+// kernels run. ks null: key bytes d_pk, else registered keys by d_idx.
+int enqueue_verify_secp_templated(cmtv_ctx* ctx, CmtvDev& D, size_t n, const uint8_t* d_pk,
+                                  const cmtv_secp_keyset* ks, const uint32_t* d_idx, const uint8_t* d_sig,
+                                  const SbFuse& sb, uint32_t max_len, const uint32_t* d_off, uint8_t* d_msg,
+                                  uint8_t* d_valid, uint64_t* d_bitmap, hipStream_t s) {
+  if (n == 0) return CMTV_OK;
+  if (!sb.tmpls || !sb.flag || !sb.sec || !sb.nanos) return CMTV_EINVAL;
+  const bool fuse = ctx->sb_fuse && max_len <= kSbFuseMaxMsg;
+  if (fuse) {
+    ctx->stats.fused_sign_bytes++;
+  } else {
+    if (!sb.tidx || !d_off || !d_msg) return CMTV_EINVAL;
+    const hipError_t e = launch_sign_bytes((uint32_t)n, sb.tmpls, sb.blob, sb.tidx, sb.flag, sb.sec, sb.nanos, d_off,
+                                           d_msg, s);
+    if (e != hipSuccess) return hip_fail(e);
+  }
+  if (ks)
+    return enqueue_verify_secp_keyed(ctx, D, ks, n, d_idx, d_sig, d_msg, d_off, d_valid, d_bitmap, s,
+                                     fuse ? &sb : nullptr);
+  return enqueue_verify_secp(ctx, D, n, d_pk, d_sig, d_msg, d_off, d_valid, d_bitmap, s, fuse ? &sb : nullptr);
 }
 
 }  // namespace cmtv

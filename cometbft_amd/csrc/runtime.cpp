@@ -486,6 +486,8 @@ void cmtv_close(cmtv_ctx* ctx) {
   ctx->pipe_ws = nullptr;
   for (auto& e : ctx->keysets) cmtv_keyset_free(e.second);
   ctx->keysets.clear();
+  for (auto* k : ctx->secp_keysets) cmtv_secp_keyset_free(k);
+  ctx->secp_keysets.clear();
   for (auto* z : ctx->zombies) cmtv_keyset_free(z);
   ctx->zombies.clear();
   drop_comms(ctx, false);

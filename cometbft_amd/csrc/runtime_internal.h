@@ -10,6 +10,7 @@
 
 struct cmtv_ctx;
 struct cmtv_keyset;
+struct cmtv_secp_keyset;
 
 namespace cmtv {
 
@@ -48,6 +49,25 @@ int verify_templated_locked(cmtv_ctx* ctx, size_t n, const uint8_t* pk, const ui
 // derived from the templates here unless the fused small-batch path, which
 // never reads them, runs the batch; between: run once the kernels are
 // enqueued, before the wait -- its answer in *between_ok)
+
+// Commit signatures over secp256k1 keys (commit_typed.cpp), sign-bytes from
+// per-commit templates as verify_templated_locked: pk33 n x 33 key bytes, or
+// (ks set) registered keys by key_idx (each below the set's size). One
+// staging block (keys or indices, signatures, flags, seconds, nanos,
+// templates, blob) to the context's first device; the lanes build their
+// messages themselves when every one fits kSbFuseMaxMsg bytes, else
+// k_sign_bytes writes them first. Verdict bytes back, the call waits for them
+// (as cmtv_verify_secp256k1). tidx null: every signature uses template 0.
+// Caller holds the context lock.
+int verify_secp_templated_locked(cmtv_ctx* ctx, size_t n, const uint8_t* pk33, const cmtv_secp_keyset* ks,
+                                 const uint32_t* key_idx, const uint8_t* sig, const void* tmpls, size_t n_tmpls,
+                                 const uint8_t* blob, size_t blob_len, const uint32_t* tidx,
+                                 const uint8_t* commit_flag, const int64_t* sec, const int32_t* nanos,
+                                 uint8_t* out_valid);
+// cmtv_keyset_cache for secp256k1 sets: the registered set of these n 33-byte
+// keys (built on first use, k_secp_qcomb_build), or NULL when the cache is
+// off or registration failed (the caller then verifies by key bytes).
+const cmtv_secp_keyset* secp_keyset_for_locked(cmtv_ctx* ctx, const uint8_t* pk33, size_t n_keys);
 
 // A single commit's n contiguous 64-byte signatures -- and, for the generic
 // kernels (pk set: the validator set's n packed 32-byte keys), its keys --

@@ -322,6 +322,7 @@ struct CmtvDev {
   // call's own staging (no other entry point touches them)
   uint32_t* d_secp_gtab = nullptr;
   DevBuf secp_in, secp_out;
+  std::vector<uint8_t> secp_stage;  // verify_secp_templated_locked's staging block, kept between calls
   DevBuf d_in, d_out, d_all;
   HostBuf h_in, h_out;
   // small single-device host batches: the kernel writes the verdict bitmap
@@ -408,6 +409,10 @@ struct cmtv_ctx {
   // key sets, used by cmtv_verify_commit(s); FIFO of at most keyset_cap
   size_t keyset_cap = 0;
   std::vector<std::pair<std::string, cmtv_keyset*>> keysets;
+  // ... and the registered secp256k1 sets of typed commits (commit_typed.cpp;
+  // keyset.cpp secp_keyset_for_locked): a list of its own under the same cap,
+  // oldest out, compared by key bytes (n x 33), never pinned
+  std::vector<cmtv_secp_keyset*> secp_keysets;
   // CMTV_FAULT_AT: 1-based index of the verification launch that fails
   uint64_t fault_at = 0, launch_seq = 0;
   bool fault_pending = false;  // the last failure was CMTV_FAULT_AT's
@@ -674,10 +679,16 @@ int enqueue_verify_keyed(cmtv_ctx* ctx, CmtvDev& D, const cmtv_keyset::PerDev& K
                          const SbFuse* sb = nullptr, uint32_t min_waves = 0);
 int enqueue_verify_secp(cmtv_ctx* ctx, CmtvDev& D, size_t n, const uint8_t* d_pk, const uint8_t* d_sig,
                         const uint8_t* d_msg, const uint32_t* d_off, uint8_t* d_valid, uint64_t* d_bitmap,
-                        hipStream_t s);
+                        hipStream_t s, const SbFuse* sb = nullptr);
 int enqueue_verify_secp_keyed(cmtv_ctx* ctx, CmtvDev& D, const cmtv_secp_keyset* ks, size_t n, const uint32_t* d_idx,
                               const uint8_t* d_sig, const uint8_t* d_msg, const uint32_t* d_off, uint8_t* d_valid,
-                              uint64_t* d_bitmap, hipStream_t s);
+                              uint64_t* d_bitmap, hipStream_t s, const SbFuse* sb = nullptr);
+// commit signatures, sign-bytes from templates: fused (max_len <= kSbFuseMaxMsg)
+// or through k_sign_bytes into d_msg at d_off
+int enqueue_verify_secp_templated(cmtv_ctx* ctx, CmtvDev& D, size_t n, const uint8_t* d_pk,
+                                  const cmtv_secp_keyset* ks, const uint32_t* d_idx, const uint8_t* d_sig,
+                                  const SbFuse& sb, uint32_t max_len, const uint32_t* d_off, uint8_t* d_msg,
+                                  uint8_t* d_valid, uint64_t* d_bitmap, hipStream_t s);
 
 // host_batch.cpp: a host batch straight to the devices (no verdict cache),
 // generic keys or (ks) registered ones; secp256k1 on devs[0]. Lock held.

@@ -47,6 +47,7 @@
 #include "fp256k1.h"
 #include "sc256k1.h"
 #include "sha256.h"
+#include "signbytes.h"
 
 namespace cmtv {
 
@@ -386,6 +387,31 @@ CMTV_HD bool secp_verify_keyed_one(bool key_ok, const uint8_t* sig, const uint8_
   secp_comb_add(acc, u1, gt);
   secp_comb_add(acc, u2, qt);
   return secp_x_is_r(acc, r) && ok;
+}
+
+// ---------------------------------------------------------------- templated sign-bytes
+// Commit signatures: the lane writes its own message, the CanonicalVote of
+// its signature from the commit's template (signbytes.h sb_write: flag,
+// seconds and nanos are the signature's), into `slot` through `out` -- a
+// byte writer over slot, the lane's LDS slot on the device -- and hashes it
+// from there: sha256_msg reads only words that hold message bytes, so the
+// lane reads nothing it did not write. The caller has checked that the
+// message fits the slot. The verdict is secp_verify_one's / keyed_one's over
+// those bytes.
+template <class Out, class QTab, class GTab>
+CMTV_HD bool secp_verify_tmpl_one(const uint8_t* pk, const uint8_t* sig, Out& out, const uint8_t* slot,
+                                  const SbTemplate& t, const uint8_t* blob, bool commit_flag, int64_t sec,
+                                  int32_t nanos, QTab& qt, const GTab& gt) {
+  const uint32_t ml = sb_write(out, t, blob, commit_flag, sec, nanos);
+  return secp_verify_one(pk, sig, slot, ml, qt, gt);
+}
+
+template <class Out, class QTab, class GTab>
+CMTV_HD bool secp_verify_keyed_tmpl_one(bool key_ok, const uint8_t* sig, Out& out, const uint8_t* slot,
+                                        const SbTemplate& t, const uint8_t* blob, bool commit_flag, int64_t sec,
+                                        int32_t nanos, const QTab& qt, const GTab& gt) {
+  const uint32_t ml = sb_write(out, t, blob, commit_flag, sec, nanos);
+  return secp_verify_keyed_one(key_ok, sig, slot, ml, qt, gt);
 }
 
 }  // namespace cmtv

@@ -14,6 +14,11 @@
 //   k_verify_secp256k1_keyed: one signature per lane by registered key
 //     (secp_verify_keyed_one): both scalar multiplications are combs, 33
 //     additions from the fixed table and 33 from the key's; no scratch.
+//   k_verify_secp256k1_tmpl, k_verify_secp256k1_keyed_tmpl: the same two with
+//     each lane's message built by the lane itself: the CanonicalVote of its
+//     commit signature written from the commit's template (kernels.h SbFuse,
+//     signbytes.h sb_write) into the lane's own LDS slot of kSbFuseMaxMsg
+//     bytes and hashed from there, so a commit ships no message buffer.
 //
 // Memory layout: pk n x 33 B and sig n x 64 B (read bytewise: a 33-byte
 // stride has no alignment), msg flat bytes + (n+1) u32 offsets as the other
@@ -143,6 +148,93 @@ __global__ __launch_bounds__(64) void k_verify_secp256k1_keyed(uint32_t n, uint3
   DevSecpGTab gt{gtab};
   bool v = secp_verify_keyed_one(in_set && key_ok[key] != 0, sig + 64 * (size_t)i, msg + m0, m1 - m0, qt, gt);
   lane_verdict_store(gid, active, v, out_valid, out_bitmap);
+}
+
+// The templated kernels' per-lane inputs, after helper_message's precedent
+// (kernel_parts.h): signature i's template (tidx null: template 0), flag and
+// timestamp, and a byte writer over this lane's LDS slot. A lane hashes only
+// bytes it wrote itself, so no barrier is needed; a lane past n rebuilds
+// signature n - 1's message in its own slot.
+struct SecpLaneMsg {
+  SbTemplate tp;
+  bool flag;
+  int64_t sec;
+  int32_t nanos;
+  __device__ __forceinline__ SecpLaneMsg(const SbFuse& sb, uint32_t i)
+      : tp(static_cast<const SbTemplate*>(sb.tmpls)[sb.tidx ? sb.tidx[i] : 0u]),
+        flag(sb.flag[i] != 0),
+        sec(sb.sec[i]),
+        nanos(sb.nanos[i]) {}
+};
+
+// k_verify_secp256k1 with templated sign-bytes (sb.tmpls set)
+__global__ __launch_bounds__(64, 2) void k_verify_secp256k1_tmpl(uint32_t n, const uint8_t* __restrict__ pk,
+                                                                 const uint8_t* __restrict__ sig, SbFuse sb,
+                                                                 const uint32_t* __restrict__ gtab,
+                                                                 uint32_t* __restrict__ qtab,
+                                                                 uint8_t* __restrict__ out_valid,
+                                                                 uint64_t* __restrict__ out_bitmap) {
+  __shared__ uint32_t slots[64][kSbFuseMaxMsg / 4];
+  const uint32_t gid = blockIdx.x * 64 + threadIdx.x;
+  const bool active = gid < n;
+  const uint32_t i = active ? gid : n - 1;
+  const SecpLaneMsg m(sb, i);
+  uint8_t* slot = reinterpret_cast<uint8_t*>(slots[threadIdx.x]);
+  LdsBytes out{slot};
+  DevSecpQTab qt{qtab, gridDim.x * 64u, gid};
+  DevSecpGTab gt{gtab};
+  bool v = secp_verify_tmpl_one(pk + 33 * (size_t)i, sig + 64 * (size_t)i, out, slot, m.tp, sb.blob, m.flag, m.sec,
+                                m.nanos, qt, gt);
+  lane_verdict_store(gid, active, v, out_valid, out_bitmap);
+}
+
+// k_verify_secp256k1_keyed with templated sign-bytes
+__global__ __launch_bounds__(64) void k_verify_secp256k1_keyed_tmpl(uint32_t n, uint32_t n_keys,
+                                                                    const uint32_t* __restrict__ key_idx,
+                                                                    const uint8_t* __restrict__ key_ok,
+                                                                    const uint32_t* __restrict__ qtab,
+                                                                    const uint8_t* __restrict__ sig, SbFuse sb,
+                                                                    const uint32_t* __restrict__ gtab,
+                                                                    uint8_t* __restrict__ out_valid,
+                                                                    uint64_t* __restrict__ out_bitmap) {
+  __shared__ uint32_t slots[64][kSbFuseMaxMsg / 4];
+  const uint32_t gid = blockIdx.x * 64 + threadIdx.x;
+  const bool active = gid < n;
+  const uint32_t i = active ? gid : n - 1;
+  const SecpLaneMsg m(sb, i);
+  uint8_t* slot = reinterpret_cast<uint8_t*>(slots[threadIdx.x]);
+  LdsBytes out{slot};
+  const uint32_t k = key_idx[i];
+  const bool in_set = k < n_keys;
+  const uint32_t key = in_set ? k : 0;
+  DevSecpGTab qt{qtab + (size_t)key * kSecpGtabWords};
+  DevSecpGTab gt{gtab};
+  bool v = secp_verify_keyed_tmpl_one(in_set && key_ok[key] != 0, sig + 64 * (size_t)i, out, slot, m.tp, sb.blob,
+                                      m.flag, m.sec, m.nanos, qt, gt);
+  lane_verdict_store(gid, active, v, out_valid, out_bitmap);
+}
+
+hipError_t launch_verify_secp256k1_tmpl(uint32_t n, const void* pk, const void* sig, const SbFuse& sb,
+                                        const uint32_t* gtab, uint32_t* qtab, void* valid, void* bitmap,
+                                        hipStream_t s) {
+  if (n == 0) return hipSuccess;
+  if (!sb.tmpls) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_verify_secp256k1_tmpl, dim3((n + 63) / 64), dim3(64), 0, s, n,
+                     static_cast<const uint8_t*>(pk), static_cast<const uint8_t*>(sig), sb, gtab, qtab,
+                     static_cast<uint8_t*>(valid), static_cast<uint64_t*>(bitmap));
+  return hipGetLastError();
+}
+
+hipError_t launch_verify_secp256k1_keyed_tmpl(uint32_t n, uint32_t n_keys, const uint32_t* key_idx,
+                                              const uint8_t* key_ok, const uint32_t* qtab, const void* sig,
+                                              const SbFuse& sb, const uint32_t* gtab, void* valid, void* bitmap,
+                                              hipStream_t s) {
+  if (n == 0) return hipSuccess;
+  if (!sb.tmpls) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_verify_secp256k1_keyed_tmpl, dim3((n + 63) / 64), dim3(64), 0, s, n, n_keys, key_idx, key_ok,
+                     qtab, static_cast<const uint8_t*>(sig), sb, gtab, static_cast<uint8_t*>(valid),
+                     static_cast<uint64_t*>(bitmap));
+  return hipGetLastError();
 }
 
 hipError_t launch_secp_qcomb_build(uint32_t n_keys, const uint8_t* d_pk, uint8_t* d_ok, uint32_t* d_tab,

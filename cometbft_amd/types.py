@@ -25,6 +25,7 @@ from typing import Optional, Sequence
 import numpy as np
 
 from . import _native as N
+from . import ripemd160 as _ripemd160
 from .crypto import MODE_GO_STDLIB, Context, default_context
 
 BLOCK_ID_FLAG_ABSENT = 1
@@ -165,11 +166,17 @@ class Validator:
     pub_key: bytes
     voting_power: int
     proposer_priority: int = 0
+    key_type: str = "ed25519"  # or "secp256k1", "sr25519" (types/params.go ABCIPubKeyType*)
 
     @property
     def address(self) -> bytes:
-        """PubKey.Address(): SHA-256(pubkey)[:20] (crypto/ed25519/ed25519.go:136)."""
-        return hashlib.sha256(self.pub_key).digest()[:20]
+        """PubKey.Address(): SHA-256(pubkey)[:20] for Ed25519 and sr25519
+        (crypto/ed25519/ed25519.go:136, crypto/sr25519/pubkey.go:27),
+        RIPEMD160(SHA-256(pubkey)) for secp256k1 (crypto/secp256k1/secp256k1.go:152)."""
+        if self.key_type not in N.KEY_TYPES:
+            raise ValueError(f"unknown key type {self.key_type!r}")
+        h = hashlib.sha256(self.pub_key).digest()
+        return _ripemd160.ripemd160(h) if self.key_type == "secp256k1" else h[:20]
 
 
 class ValidatorSet:
@@ -193,8 +200,9 @@ class ValidatorSet:
             vp = np.array([v.voting_power for v in vals] + [0], np.int64)
             pp = np.array([v.proposer_priority for v in vals] + [0], np.int64)
             ad = np.frombuffer(b"".join(v.address for v in vals) + b"\0", np.uint8).copy()
-            self._packed = (pk, off, vp, pp, ad)
-        pk, off, vp, pp, ad = self._packed
+            kt = np.array([N.KEY_TYPES[v.key_type] for v in vals] + [0], np.uint8)
+            self._packed = (pk, off, vp, pp, ad, kt)
+        pk, off, vp, pp, ad, kt = self._packed
         s = N.cmtv_valset(n_vals=len(self.validators), pubkeys=_p8(pk), pk_off=_p32(off),
                           voting_power=vp.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), addrs=_p8(ad),
                           proposer_priority=pp.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)))
@@ -272,8 +280,13 @@ def _verify(vals: ValidatorSet, kind, chain_id, block_id, height, commit, num, d
     res = N.cmtv_commit_result()
     buf = ctypes.create_string_buffer(4096)
     cid = chain_id.encode()
-    rc = N.lib().cmtv_verify_commit(ctx.handle, kind, mode, cid, len(cid), ctypes.byref(vs), bidp, height,
-                                    ctypes.byref(cm), num, den, ctypes.byref(res), buf, len(buf))
+    kt = keep_v[5]
+    if kt[:-1].any():  # a validator that is not Ed25519: the typed entry point
+        rc = N.lib().cmtv_verify_commit_typed(ctx.handle, kind, mode, cid, len(cid), ctypes.byref(vs), _p8(kt), bidp,
+                                              height, ctypes.byref(cm), num, den, ctypes.byref(res), buf, len(buf))
+    else:
+        rc = N.lib().cmtv_verify_commit(ctx.handle, kind, mode, cid, len(cid), ctypes.byref(vs), bidp, height,
+                                        ctypes.byref(cm), num, den, ctypes.byref(res), buf, len(buf))
     N.check(rc, "cmtv_verify_commit")
     err = _error_for(rc, res, buf.value.decode())
     if err is not None:

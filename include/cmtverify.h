@@ -520,6 +520,48 @@ int cmtv_verify_commit(cmtv_ctx* ctx, uint32_t kind, uint32_t mode, const char* 
                        const cmtv_commit* commit, uint64_t trust_num, uint64_t trust_den, cmtv_commit_result* res,
                        char* msg_buf, size_t msg_cap);
 
+/* Validator sets of other key types (types/params.go ABCIPubKeyTypeEd25519 /
+ * Secp256k1 / Sr25519), and sets that mix them. key_types holds one
+ * CMTV_KEY_* per validator of vals (NULL: every key is Ed25519). The outcome,
+ * *res and the error string are those of the reference's VerifyCommit* with
+ * each validator's PubKey of the stated type, whose VerifySignature the
+ * reference loop calls (types/validator_set.go:695, 751, 812):
+ *   - key_types NULL or all CMTV_KEY_ED25519: the call IS cmtv_verify_commit
+ *     (same code, same fast paths, same bytes out).
+ *   - a value above CMTV_KEY_SR25519, or a secp256k1 key of 65 bytes (the
+ *     uncompressed encoding, which the key codec never yields,
+ *     crypto/encoding/codec.go:53): CMTV_EINVAL.
+ *   - Ed25519 validators as in cmtv_verify_commit, a key that is not 32 bytes
+ *     being CMTV_COMMIT_PANIC_BAD_PUBKEY after the signature-length check;
+ *     `mode` applies to them only.
+ *   - secp256k1 (crypto/secp256k1/secp256k1.go:192-217): a signature that is
+ *     not 64 bytes, a key that is not 33 bytes or that ParsePubKey rejects,
+ *     a high-S signature: "wrong signature (#i): ...", never a panic.
+ *   - sr25519 (crypto/sr25519/pubkey.go:36-60): a signature that is not 64
+ *     bytes is wrong; the key is copied into a zeroed 32-byte array, so a key
+ *     of any length is truncated or zero-padded.
+ *   - the double-vote error prints the validator's key as PubKeyEd25519{..},
+ *     PubKeySecp256k1{..} or PubKeySr25519{..}; CMTV_VERIFY_COMMIT_LIGHT_TRUSTING
+ *     matches by vals->addrs as ever (a secp256k1 address is
+ *     RIPEMD160(SHA256(key)), the caller's to compute).
+ * The planned signatures are split by type: the Ed25519 part runs the
+ * templated batch of cmtv_verify_commit, the secp256k1 part kernels that
+ * build each CanonicalVote from the commit's template on the device (no
+ * message buffer is shipped), the sr25519 part sign-bytes encoded on the host
+ * and the batch behind cmtv_verify_sr25519 (no templated sr25519 kernel yet).
+ * res->n_verified counts all three. With cmtv_keyset_cache on, a set whose
+ * validators are all secp256k1 with keys packed at 33 bytes is registered on
+ * its first call (528 KiB per key on the first device) and later calls use
+ * the registered-key kernel; mixed sets use key bytes. A typed call never
+ * enters the cross-height pipeline or the speculative path, and its Ed25519
+ * and secp256k1 parts do not consult cmtv_verdict_cache. Cross-height typed
+ * batching is out of scope: cmtv_verify_commits has no typed form. */
+enum { CMTV_KEY_ED25519 = 0, CMTV_KEY_SECP256K1 = 1, CMTV_KEY_SR25519 = 2 };
+int cmtv_verify_commit_typed(cmtv_ctx* ctx, uint32_t kind, uint32_t mode, const char* chain_id, size_t chain_id_len,
+                             const cmtv_valset* vals, const uint8_t* key_types, const cmtv_block_id* block_id,
+                             int64_t height, const cmtv_commit* commit, uint64_t trust_num, uint64_t trust_den,
+                             cmtv_commit_result* res, char* msg_buf, size_t msg_cap);
+
 /* Cross-height batching (blocksync / light-client replay):
  * n commits, each with its own validator set, block ID and height, verified
  * with ONE device batch for all their signatures, then each commit's
