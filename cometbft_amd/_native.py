@@ -56,7 +56,7 @@ EXPORTS = (
     "cmtv_register_keys", "cmtv_register_keys_ex", "cmtv_keyset_free", "cmtv_keyset_len", "cmtv_verify_ed25519_indexed",
     "cmtv_verify_ed25519_indexed_device",
     "cmtv_batch_new", "cmtv_batch_add", "cmtv_batch_len", "cmtv_batch_verify", "cmtv_batch_reset",
-    "cmtv_batch_free", "cmtv_verify_commit", "cmtv_verify_commit_typed", "cmtv_verify_commits", "cmtv_verdict_cache", "cmtv_keyset_cache", "cmtv_vote_sign_bytes", "cmtv_pubkeys_ed25519", "cmtv_sign_ed25519",
+    "cmtv_batch_free", "cmtv_verify_commit", "cmtv_verify_commit_typed", "cmtv_verify_commits", "cmtv_verify_commits_typed", "cmtv_verdict_cache", "cmtv_keyset_cache", "cmtv_vote_sign_bytes", "cmtv_pubkeys_ed25519", "cmtv_sign_ed25519",
     "cmtv_alloc_pinned", "cmtv_free_pinned",
 )
 
@@ -82,7 +82,7 @@ class cmtv_stats(ctypes.Structure):
                 ("faults_injected", ctypes.c_uint64), ("n_devices", ctypes.c_uint32), ("rccl", ctypes.c_uint32),
                 ("fused_sign_bytes", ctypes.c_uint64), ("device_failures", ctypes.c_uint64),
                 ("reshards", ctypes.c_uint64), ("late_k_waves", ctypes.c_uint64),
-                ("live_devices", ctypes.c_uint32), ("reserved", ctypes.c_uint32),
+                ("live_devices", ctypes.c_uint32), ("secp_batch_launches", ctypes.c_uint32),
                 ("timed_calls", ctypes.c_uint64), ("rccl_failures", ctypes.c_uint64),
                 ("polled_calls", ctypes.c_uint64), ("direct_chunks", ctypes.c_uint64),
                 ("masked_chunks", ctypes.c_uint64), ("isolated_calls", ctypes.c_uint64)]
@@ -224,6 +224,11 @@ def lib() -> ctypes.CDLL:
                                       u64, u64, ctypes.POINTER(cmtv_commit_result), ctypes.POINTER(ctypes.c_int),
                                       ctypes.c_char_p, sz]
     L.cmtv_verify_commits.restype = ctypes.c_int
+    L.cmtv_verify_commits_typed.argtypes = [vp, u32, u32, ctypes.c_char_p, sz, sz, ctypes.POINTER(cmtv_valset),
+                                            ctypes.POINTER(_u8p), ctypes.POINTER(cmtv_block_id), ctypes.POINTER(i64),
+                                            ctypes.POINTER(cmtv_commit), u64, u64, ctypes.POINTER(cmtv_commit_result),
+                                            ctypes.POINTER(ctypes.c_int), ctypes.c_char_p, sz]
+    L.cmtv_verify_commits_typed.restype = ctypes.c_int
     L.cmtv_keyset_cache.argtypes = [vp, sz]
     L.cmtv_keyset_cache.restype = ctypes.c_int
     L.cmtv_verdict_cache.argtypes = [vp, sz]

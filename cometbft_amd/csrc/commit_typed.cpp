@@ -20,8 +20,9 @@
 //              sr25519 kernel yet
 //
 // A set with no key of another type is forwarded to cmtv_verify_commit. Typed
-// calls never enter the cross-height pipeline or the speculative path, and
-// cmtv_verify_commits has no typed form. The calls into the runtime that
+// calls never enter the cross-height pipeline or the speculative path; many
+// heights in one call are commits_typed.cpp (cmtv_verify_commits_typed), with
+// the partition shared in commit_typed_parts.h. The calls into the runtime that
 // commit.cpp does not make live here only: commit.cpp and pipeline.cpp link
 // without them.
 #include <hip/hip_runtime.h>
@@ -33,55 +34,13 @@
 
 #include "../../include/cmtverify.h"
 #include "commit_internal.h"
+#include "commit_typed_parts.h"
 #include "runtime_internal.h"
 #include "signbytes.h"
 
 namespace {
 
 using namespace cmtv;
-
-// Byte writer (signbytes.h sb_write) into host memory
-struct HostBytes {
-  uint8_t* p;
-  void put(uint32_t pos, uint8_t b) { p[pos] = b; }
-  void copy(uint32_t pos, const uint8_t* src, uint32_t len) {
-    if (len) std::memcpy(p + pos, src, len);
-  }
-};
-
-// One key type's share of the plan: plan positions and the per-signature
-// arrays its batch reads
-struct Part {
-  std::vector<uint32_t> at;  // plan item of each entry
-  std::vector<uint8_t> pk, sg, flag;
-  std::vector<int64_t> sec;
-  std::vector<int32_t> nanos;
-  std::vector<uint32_t> kidx;
-  size_t size() const { return at.size(); }
-  void reserve(size_t n, size_t key_width) {
-    at.reserve(n);
-    pk.reserve(key_width * n);
-    sg.reserve(64 * n);
-    flag.reserve(n);
-    sec.reserve(n);
-    nanos.reserve(n);
-    kidx.reserve(n);
-  }
-  void add(uint32_t j, const uint8_t* key, size_t key_len, size_t key_width, const uint8_t* sig, bool for_block,
-           int64_t s, int32_t ns, uint32_t vi) {
-    at.push_back(j);
-    // the key in a zeroed array of the type's width (sr25519: truncated or
-    // zero-padded, crypto/sr25519/pubkey.go:36-45; the others arrive whole)
-    const size_t o = pk.size();
-    pk.resize(o + key_width, 0);
-    std::memcpy(&pk[o], key, key_len < key_width ? key_len : key_width);
-    sg.insert(sg.end(), sig, sig + 64);
-    flag.push_back(for_block ? 1 : 0);
-    sec.push_back(s);
-    nanos.push_back(ns);
-    kidx.push_back(vi);
-  }
-};
 
 int verify_typed(cmtv_ctx* ctx, uint32_t kind, uint32_t mode, const char* chain_id, size_t chain_id_len,
                  const cmtv_valset* vals, const uint8_t* key_types, const cmtv_block_id* block_id, int64_t height,
@@ -167,28 +126,15 @@ int verify_typed(cmtv_ctx* ctx, uint32_t kind, uint32_t mode, const char* chain_
                                       commit->ts_seconds, commit->ts_nanos, valid.data());
     if (rc != CMTV_OK) return rc;
   } else {
-    // partition: a signature that is not 64 bytes is wrong for every type
-    // before its key is looked at, and a secp256k1 key that is not 33 bytes
-    // fails ParsePubKey: neither goes to a device, their verdict stays 0
+    // partition (commit_typed_parts.h): a signature that is not 64 bytes, or
+    // a secp256k1 key that is not 33, goes to no device: its verdict stays 0
     Part ed, secp, sr;
     size_t count[3] = {0, 0, 0};
     for (size_t j = 0; j < m; j++) count[key_types[J.plan_val[j]]]++;
     ed.reserve(count[CMTV_KEY_ED25519], 32);
     secp.reserve(count[CMTV_KEY_SECP256K1], 33);
     sr.reserve(count[CMTV_KEY_SR25519], 32);
-    for (size_t j = 0; j < m; j++) {
-      const uint32_t idx = J.plan_idx[j], vi = J.plan_val[j];
-      const uint32_t s0 = commit->sig_off[idx], s1 = commit->sig_off[idx + 1];
-      if (s1 - s0 != 64) continue;
-      const uint8_t* key = vals->pubkeys + vals->pk_off[vi];
-      const size_t kl = vals->pk_off[vi + 1] - vals->pk_off[vi];
-      const bool for_block = commit->flags[idx] == kFlagCommit;
-      const uint8_t t = key_types[vi];
-      if (t == CMTV_KEY_SECP256K1 && kl != 33) continue;
-      Part& P = t == CMTV_KEY_ED25519 ? ed : t == CMTV_KEY_SECP256K1 ? secp : sr;
-      P.add((uint32_t)j, key, kl, t == CMTV_KEY_SECP256K1 ? 33 : 32, commit->sigs + s0, for_block,
-            commit->ts_seconds[idx], commit->ts_nanos[idx], vi);
-    }
+    partition_plan(J, m, 0, 0, ed, secp, sr);
     phase_add(ctx, kPhPrepare, t0);
 
     auto scatter = [&](const Part& P) {

@@ -747,12 +747,12 @@ int verify_secp_keyed_host_locked(cmtv_ctx* ctx, const cmtv_secp_keyset* ks, siz
 //   (n + 1, non-fused only) | templates | sig | pk (n x 33) | flag | blob
 // with the 8-byte array first and the 4-byte ones next, so every array the
 // kernels read as int64 / int32 is aligned whatever n is; on the device the
-// non-fused route's messages follow it.
-int verify_secp_templated_locked(cmtv_ctx* ctx, size_t n, const uint8_t* pk33, const cmtv_secp_keyset* ks,
-                                 const uint32_t* key_idx, const uint8_t* sig, const void* tmpls, size_t n_tmpls,
-                                 const uint8_t* blob, size_t blob_len, const uint32_t* tidx,
-                                 const uint8_t* commit_flag, const int64_t* sec, const int32_t* nanos,
-                                 uint8_t* out_valid) {
+// non-fused route's messages follow it. bulk: the fused registered-key route
+// may take the batched kernel (launch.cpp enqueue_verify_secp_keyed).
+static int secp_templated(cmtv_ctx* ctx, size_t n, const uint8_t* pk33, const cmtv_secp_keyset* ks,
+                          const uint32_t* key_idx, const uint8_t* sig, const void* tmpls, size_t n_tmpls,
+                          const uint8_t* blob, size_t blob_len, const uint32_t* tidx, const uint8_t* commit_flag,
+                          const int64_t* sec, const int32_t* nanos, uint8_t* out_valid, bool bulk) {
   if (n == 0) return CMTV_OK;
   if (!sig || !tmpls || !n_tmpls || !commit_flag || !sec || !nanos || (ks ? !key_idx : !pk33)) return CMTV_EINVAL;
   if (ctx->devs.empty() || ctx->devs[0].failed) return CMTV_ENODEV;
@@ -820,7 +820,7 @@ int verify_secp_templated_locked(cmtv_ctx* ctx, size_t n, const uint8_t* pk33, c
   auto* dbm = static_cast<uint64_t*>(D.secp_out.p);
   const int rc = enqueue_verify_secp_templated(ctx, D, n, din + o_pk, ks, reinterpret_cast<const uint32_t*>(din + o_kidx),
                                                din + o_sig, sb, max_len, reinterpret_cast<const uint32_t*>(din + o_off),
-                                               din + o_msg, nullptr, dbm, s);
+                                               din + o_msg, nullptr, dbm, s, bulk);
   if (rc != CMTV_OK) {
     (void)hipStreamSynchronize(s);  // the copy reads the staging
     return rc;
@@ -830,6 +830,24 @@ int verify_secp_templated_locked(cmtv_ctx* ctx, size_t n, const uint8_t* pk33, c
   if ((e = wait_stream(ctx, s)) != hipSuccess) return hip_fail(e);
   ctx->stats.invalid += bitmap_tail(bm.data(), n, nullptr, out_valid);
   return CMTV_OK;
+}
+
+int verify_secp_templated_locked(cmtv_ctx* ctx, size_t n, const uint8_t* pk33, const cmtv_secp_keyset* ks,
+                                 const uint32_t* key_idx, const uint8_t* sig, const void* tmpls, size_t n_tmpls,
+                                 const uint8_t* blob, size_t blob_len, const uint32_t* tidx,
+                                 const uint8_t* commit_flag, const int64_t* sec, const int32_t* nanos,
+                                 uint8_t* out_valid) {
+  return secp_templated(ctx, n, pk33, ks, key_idx, sig, tmpls, n_tmpls, blob, blob_len, tidx, commit_flag, sec, nanos,
+                        out_valid, false);
+}
+
+int verify_secp_templated_bulk_locked(cmtv_ctx* ctx, size_t n, const uint8_t* pk33, const cmtv_secp_keyset* ks,
+                                      const uint32_t* key_idx, const uint8_t* sig, const void* tmpls, size_t n_tmpls,
+                                      const uint8_t* blob, size_t blob_len, const uint32_t* tidx,
+                                      const uint8_t* commit_flag, const int64_t* sec, const int32_t* nanos,
+                                      uint8_t* out_valid) {
+  return secp_templated(ctx, n, pk33, ks, key_idx, sig, tmpls, n_tmpls, blob, blob_len, tidx, commit_flag, sec, nanos,
+                        out_valid, true);
 }
 
 }  // namespace cmtv

@@ -151,6 +151,15 @@ hipError_t launch_verify_secp256k1_keyed_tmpl(uint32_t n, uint32_t n_keys, const
                                               const uint8_t* key_ok, const uint32_t* qtab, const void* sig,
                                               const SbFuse& sb, const uint32_t* gtab, void* valid, void* bitmap,
                                               hipStream_t s);
+// the keyed templated kernel with kb = 4 or 8 signatures per lane sharing one
+// inversion mod n (k_verify_secp256k1_keyed_batch): ceil(n / (64 kb))
+// workgroups; pre: that many x 64 lanes x kb x kSecpBatchScratchWordsPerSig
+// words of scratch (each lane's running products)
+constexpr uint32_t kSecpBatchScratchWordsPerSig = 8;
+hipError_t launch_verify_secp256k1_keyed_batch(uint32_t kb, uint32_t n, uint32_t n_keys, const uint32_t* key_idx,
+                                               const uint8_t* key_ok, const uint32_t* qtab, const void* sig,
+                                               const SbFuse& sb, const uint32_t* gtab, uint32_t* pre, void* valid,
+                                               void* bitmap, hipStream_t s);
 hipError_t launch_sign_bytes(uint32_t n, const void* tmpls, const uint8_t* blob, const uint32_t* tidx,
                              const uint8_t* commit_flag, const int64_t* sec, const int32_t* nanos,
                              const uint32_t* off, uint8_t* msg, hipStream_t s);

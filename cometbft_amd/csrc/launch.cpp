@@ -174,14 +174,7 @@ int enqueue_verify_keyed(cmtv_ctx* ctx, CmtvDev& D, const cmtv_keyset::PerDev& K
   // configs[2]'s 15M against 37.8 ms: 2,093 waves start a second, nearly
   // empty round)
   const size_t chunk = batch ? kKeyedBatchChunk : kChunk;
-  auto kb_for = [&](size_t cn) -> uint32_t {  // 4 or 8 (the instantiated forms), else 1
-    // the widest KB that still launches keyed_batch_min_waves waves (the last
-    // one may be partial: a commit-aligned 1,048,500-signature chunk takes KB
-    // = 8 in 2,048 waves)
-    uint32_t kb = 1;
-    while (kb < 8 && cn > ((size_t)min_waves - 1) * 64 * (kb * 2)) kb *= 2;
-    return batch && kb >= 4 ? kb : 1;
-  };
+  auto kb_for = [&](size_t cn) -> uint32_t { return batch ? keyed_batch_kb(cn, min_waves) : 1; };
   hipError_t e;
   const uint32_t kb0 = kb_for(std::min(chunk, n));
   if (kb0 > 1) {
@@ -287,20 +280,43 @@ int enqueue_verify_secp(cmtv_ctx* ctx, CmtvDev& D, size_t n, const uint8_t* d_pk
 }
 
 // The same by registered keys (keyset.cpp cmtv_register_keys_secp256k1):
-// d_idx n key indices in place of the key bytes; no scratch.
+// d_idx n key indices in place of the key bytes; no scratch. batch (templated
+// sign-bytes only; the cross-height typed batches): launches of
+// kKeyedBatchChunk signatures, KB per lane sharing one inversion mod n
+// (k_verify_secp256k1_keyed_batch) while keyed_batch_kb finds secp_batch_min_waves
+// waves for it; the lanes' running products in the device's scratch.
 int enqueue_verify_secp_keyed(cmtv_ctx* ctx, CmtvDev& D, const cmtv_secp_keyset* ks, size_t n, const uint32_t* d_idx,
                               const uint8_t* d_sig, const uint8_t* d_msg, const uint32_t* d_off, uint8_t* d_valid,
-                              uint64_t* d_bitmap, hipStream_t s, const SbFuse* sb) {
+                              uint64_t* d_bitmap, hipStream_t s, const SbFuse* sb, bool batch) {
   if (n == 0) return CMTV_OK;
   if (fault_hit(ctx) || D.inject_fault) return CMTV_EHIP;
   hipError_t e = ensure_secp_gtab(D);
   if (e != hipSuccess) return hip_fail(e);
+  const uint32_t min_waves = ctx->secp_batch_min_waves;
+  auto kb_for = [&](size_t cn) -> uint32_t { return keyed_batch_kb(cn, min_waves, ctx->secp_batch_max_kb); };
+  batch = batch && sb && min_waves != 0 && kb_for(std::min<size_t>(kKeyedBatchChunk, n)) > 1;
+  Scratch& S = D.scratch;
+  if (batch) {
+    // the first chunk is the largest: kb and lanes shrink together
+    const size_t cn = std::min<size_t>(kKeyedBatchChunk, n);
+    const uint32_t kb = kb_for(cn);
+    const size_t lanes = (cn + 64 * kb - 1) / (64 * kb) * 64;
+    if ((e = acquire_scratch(S, lanes * kb * kSecpBatchScratchWordsPerSig * sizeof(uint32_t), s)) != hipSuccess)
+      return hip_fail(e);
+  }
   LaunchScope L{ctx, D, s};
   if ((e = L.begin()) != hipSuccess) return hip_fail(e);
-  const size_t chunk = ctx->lane_chunk;
+  const size_t chunk = batch ? (size_t)kKeyedBatchChunk : ctx->lane_chunk;
   for (size_t c = 0; c < n; c += chunk) {
     const uint32_t cn = (uint32_t)std::min<size_t>(chunk, n - c);
-    if (sb)
+    const uint32_t kb = batch ? kb_for(cn) : 1;
+    if (kb > 1) {
+      e = launch_verify_secp256k1_keyed_batch(kb, cn, (uint32_t)ks->n, d_idx + c, ks->d_ok, ks->d_tab, d_sig + 64 * c,
+                                              sb_at(*sb, c), D.d_secp_gtab, static_cast<uint32_t*>(S.buf.p),
+                                              d_valid ? d_valid + c : nullptr, d_bitmap ? d_bitmap + c / 64 : nullptr,
+                                              s);
+      if (e == hipSuccess) ctx->stats.secp_batch_launches++;
+    } else if (sb)
       e = launch_verify_secp256k1_keyed_tmpl(cn, (uint32_t)ks->n, d_idx + c, ks->d_ok, ks->d_tab, d_sig + 64 * c,
                                              sb_at(*sb, c), D.d_secp_gtab, d_valid ? d_valid + c : nullptr,
                                              d_bitmap ? d_bitmap + c / 64 : nullptr, s);
@@ -311,18 +327,19 @@ int enqueue_verify_secp_keyed(cmtv_ctx* ctx, CmtvDev& D, const cmtv_secp_keyset*
     if ((e = L.launched(e)) != hipSuccess) return hip_fail(e);
     ctx->stats.keyed_launches++;
   }
-  return L.finish(n, nullptr);
+  return L.finish(n, batch ? &S : nullptr);
 }
 
 // Commit signatures over secp256k1 keys, sign-bytes from the commits'
 // templates: the templated kernels when every message fits a lane's LDS slot
 // (max_len <= kSbFuseMaxMsg); otherwise k_sign_bytes writes the messages to
 // d_msg at the offsets d_off (sb.tidx set then) and the message-reading
-// kernels run. ks null: key bytes d_pk, else registered keys by d_idx.
+// kernels run. ks null: key bytes d_pk, else registered keys by d_idx. batch:
+// the fused registered-key route may take the batched kernel.
 int enqueue_verify_secp_templated(cmtv_ctx* ctx, CmtvDev& D, size_t n, const uint8_t* d_pk,
                                   const cmtv_secp_keyset* ks, const uint32_t* d_idx, const uint8_t* d_sig,
                                   const SbFuse& sb, uint32_t max_len, const uint32_t* d_off, uint8_t* d_msg,
-                                  uint8_t* d_valid, uint64_t* d_bitmap, hipStream_t s) {
+                                  uint8_t* d_valid, uint64_t* d_bitmap, hipStream_t s, bool batch) {
   if (n == 0) return CMTV_OK;
   if (!sb.tmpls || !sb.flag || !sb.sec || !sb.nanos) return CMTV_EINVAL;
   const bool fuse = ctx->sb_fuse && max_len <= kSbFuseMaxMsg;
@@ -336,7 +353,7 @@ int enqueue_verify_secp_templated(cmtv_ctx* ctx, CmtvDev& D, size_t n, const uin
   }
   if (ks)
     return enqueue_verify_secp_keyed(ctx, D, ks, n, d_idx, d_sig, d_msg, d_off, d_valid, d_bitmap, s,
-                                     fuse ? &sb : nullptr);
+                                     fuse ? &sb : nullptr, batch);
   return enqueue_verify_secp(ctx, D, n, d_pk, d_sig, d_msg, d_off, d_valid, d_bitmap, s, fuse ? &sb : nullptr);
 }
 

@@ -260,6 +260,8 @@ static void read_env(cmtv_ctx* ctx) {
   if (const char* hp = std::getenv("CMTV_HOST_POLL")) ctx->host_poll = std::atoi(hp) != 0;
   if (const char* kl = std::getenv("CMTV_FORCE_K_LATE")) ctx->keyed_wait = kl[0] == '1' ? 0u : kKeyedWaitDefault;
   env_int("CMTV_KEYED_BATCH_MIN_WAVES", 1, 1l << 20, ctx->keyed_batch_min_waves);
+  env_int("CMTV_KEYED_BATCH_MIN_WAVES", 1, 1l << 20, ctx->secp_batch_min_waves);
+  if (std::getenv("CMTV_KEYED_BATCH_MIN_WAVES")) ctx->secp_batch_max_kb = 8;
   env_not("CMTV_ROW_FENCE", '0', ctx->row_fence);
   env_is("CMTV_HOST_PHASES", '1', ctx->phases_on);
   if (const char* tm = std::getenv("CMTV_TIMING")) {

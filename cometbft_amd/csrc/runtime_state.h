@@ -34,6 +34,24 @@ constexpr uint32_t kChunk = 1u << 18;  // signatures per launch (A-table scratch
 // signature, in the lane kernels' scratch buffer
 constexpr uint32_t kKeyedBatchChunk = 1u << 20;
 constexpr uint32_t kKeyedBatchMinWaves = 2048;
+// KB of a batched registered-key launch of cn signatures (4 or 8, the
+// instantiated forms, else 1: one signature per lane): the widest KB up to
+// max_kb that still launches min_waves waves (the last one may be partial: a
+// commit-aligned 1,048,500-signature chunk takes KB = 8 in 2,048 waves).
+// Shared by k_verify_keyed_batch and k_verify_secp256k1_keyed_batch.
+inline uint32_t keyed_batch_kb(size_t cn, uint32_t min_waves, uint32_t max_kb = 8) {
+  uint32_t kb = 1;
+  while (kb < max_kb && cn > ((size_t)min_waves - 1) * 64 * (kb * 2)) kb *= 2;
+  return kb >= 4 ? kb : 1;
+}
+// The same threshold for k_verify_secp256k1_keyed_batch (the cross-height
+// typed batches, launch.cpp enqueue_verify_secp_keyed), measured apart
+// (tools/bench_typed_commits.py): KB = 4 from 209,921 signatures
+// per launch (820 x 256; 105,000 lost, 210,000 gained), and never KB = 8 by
+// default: at every measured size KB = 4 took less kernel time than KB = 8.
+// CMTV_KEYED_BATCH_MIN_WAVES sets the threshold and allows KB = 8.
+constexpr uint32_t kSecpBatchMinWaves = 821;
+constexpr uint32_t kSecpBatchMaxKb = 4;
 // The batch-size bands of the verification forms (kernels.h kForm*, picked
 // by ed_form / sr_form / keyed_form below), measured on MI355X in round 4 and
 // frozen since (no more single-band tuning). CMTV_FORM forces one
@@ -437,6 +455,11 @@ struct cmtv_ctx {
   // waves a batched launch must keep (CMTV_KEYED_BATCH_MIN_WAVES; 1 batches
   // any size, the test knob that puts the corpus through the batched kernels)
   uint32_t keyed_batch_min_waves = cmtv::kKeyedBatchMinWaves;
+  // the same for the secp256k1 batched kernel, and its widest KB
+  // (CMTV_KEYED_BATCH_MIN_WAVES sets both thresholds and lifts the KB to 8;
+  // a threshold of 0: off)
+  uint32_t secp_batch_min_waves = cmtv::kSecpBatchMinWaves;
+  uint32_t secp_batch_max_kb = cmtv::kSecpBatchMaxKb;
   // devices (indices into devs) that take host batches, in shard order; the
   // RCCL communicator (when rccl) spans exactly these, rank = position
   std::vector<size_t> live;
@@ -682,13 +705,13 @@ int enqueue_verify_secp(cmtv_ctx* ctx, CmtvDev& D, size_t n, const uint8_t* d_pk
                         hipStream_t s, const SbFuse* sb = nullptr);
 int enqueue_verify_secp_keyed(cmtv_ctx* ctx, CmtvDev& D, const cmtv_secp_keyset* ks, size_t n, const uint32_t* d_idx,
                               const uint8_t* d_sig, const uint8_t* d_msg, const uint32_t* d_off, uint8_t* d_valid,
-                              uint64_t* d_bitmap, hipStream_t s, const SbFuse* sb = nullptr);
+                              uint64_t* d_bitmap, hipStream_t s, const SbFuse* sb = nullptr, bool batch = false);
 // commit signatures, sign-bytes from templates: fused (max_len <= kSbFuseMaxMsg)
 // or through k_sign_bytes into d_msg at d_off
 int enqueue_verify_secp_templated(cmtv_ctx* ctx, CmtvDev& D, size_t n, const uint8_t* d_pk,
                                   const cmtv_secp_keyset* ks, const uint32_t* d_idx, const uint8_t* d_sig,
                                   const SbFuse& sb, uint32_t max_len, const uint32_t* d_off, uint8_t* d_msg,
-                                  uint8_t* d_valid, uint64_t* d_bitmap, hipStream_t s);
+                                  uint8_t* d_valid, uint64_t* d_bitmap, hipStream_t s, bool batch = false);
 
 // host_batch.cpp: a host batch straight to the devices (no verdict cache),
 // generic keys or (ks) registered ones; secp256k1 on devs[0]. Lock held.

@@ -34,7 +34,9 @@
 //           plus a top carry; 33 additions from the fixed table
 //           (1..128) [256^j]G, j = 0..32 (GTab policy), no doublings
 //   registered keys (secp_verify_keyed_one): [u2]Q by the same comb over the
-//           key's own table (1..128) [256^j]Q (secp_qcomb_position)
+//           key's own table (1..128) [256^j]Q (secp_qcomb_position); with KB
+//           signatures per lane sharing the inversion 1 / s
+//           (secp_verify_keyed_batch_lane, for launches of many commits)
 // Every lane does every step whatever its inputs (verification handles public
 // data: this is for wave uniformity, not constant time); a failed check only
 // clears the verdict.
@@ -207,26 +209,42 @@ CMTV_HD bool secp_parse_pubkey(pt256& q, const uint8_t* pk) {
   return ok;
 }
 
-// The checks and scalars every verdict starts with (steps 2 and 3 and the
-// inversion of step 4): r, u1 = e / s, u2 = r / s; false when r or s is zero
-// or s is above (n - 1) / 2 (the scalars are then still defined: every lane
-// goes on).
-CMTV_HD bool secp_scalars(scn& r, scn& u1, scn& u2, const uint8_t* sig, const uint8_t* msg, uint32_t mlen) {
+// Step 2: r and s from the signature's bytes, reduced; false when r or s is
+// zero or s is above (n - 1) / 2 (the scalars are then still defined: every
+// lane goes on).
+CMTV_HD bool secp_sig_scalars(scn& r, scn& s, const uint8_t* sig) {
   uint32_t rw[8], sw[8];
   words_from_be32(rw, sig);
   words_from_be32(sw, sig + 32);
-  scn s, e, w;
   scn_from_words(r, rw);
   scn_from_words(s, sw);
-  const bool ok = !scn_is_zero(r) && !scn_is_zero(s) && !scn_over_half(s);
+  return !scn_is_zero(r) && !scn_is_zero(s) && !scn_over_half(s);
+}
+
+// Step 3: e = SHA-256(msg) mod n
+CMTV_HD void secp_msg_scalar(scn& e, const uint8_t* msg, uint32_t mlen) {
   uint32_t h[8], hw[8];
   sha256_msg(h, msg, mlen);
 #pragma unroll
   for (int i = 0; i < 8; i++) hw[i] = h[7 - i];
   scn_from_words(e, hw);
-  scn_invert(w, s);
+}
+
+// The products of step 4 for a given w = 1 / s: u1 = e w, u2 = r w
+CMTV_HD void secp_u1_u2(scn& u1, scn& u2, const scn& e, const scn& r, const scn& w) {
   scn_mul(u1, e, w);
   scn_mul(u2, r, w);
+}
+
+// The checks and scalars every verdict starts with (steps 2 and 3 and the
+// inversion of step 4): r, u1 = e / s, u2 = r / s; the verdict of
+// secp_sig_scalars.
+CMTV_HD bool secp_scalars(scn& r, scn& u1, scn& u2, const uint8_t* sig, const uint8_t* msg, uint32_t mlen) {
+  scn s, e, w;
+  const bool ok = secp_sig_scalars(r, s, sig);
+  secp_msg_scalar(e, msg, mlen);
+  scn_invert(w, s);
+  secp_u1_u2(u1, u2, e, r, w);
   return ok;
 }
 
@@ -412,6 +430,80 @@ CMTV_HD bool secp_verify_keyed_tmpl_one(bool key_ok, const uint8_t* sig, Out& ou
                                         int32_t nanos, const QTab& qt, const GTab& gt) {
   const uint32_t ml = sb_write(out, t, blob, commit_flag, sec, nanos);
   return secp_verify_keyed_one(key_ok, sig, slot, ml, qt, gt);
+}
+
+// ---------------------------------------------------------------- KB signatures per lane
+// Registered-key verification with KB signatures per lane sharing one
+// inversion mod n (Montgomery's trick: one scn_invert and 3 (KB - 1) scalar
+// products instead of KB inversions; 1/s is 63k of a keyed verification's
+// 144k multiply-adds, a scalar product 139).
+//
+// Src gives the lane its rounds: active(r), sig(r) (64 bytes; an inactive
+// round's are some signature's), key(r, qt) (whether the key is in the set
+// and accepted; qt its table), message(r, msg) (the round's message, written
+// by the lane itself on the device: its length) and verdict(r, v). Pre holds
+// the lane's KB running products: store(r, x) / load(r, x).
+//
+// Pass 1, per round: r and s and the checks of secp_sig_scalars; the running
+// product of the s values, where a zero s and an inactive round enter as 1 so
+// they cannot spoil the lane's other signatures (their verdicts are false by
+// the ok bit). One inversion. Pass 2, rounds descending: w = 1 / s_r from
+// the inverse and the product before it, then what secp_verify_keyed_one
+// does with it. Scalars are always fully reduced (sc256k1.h), so w, u1 and u2
+// are the words the one-signature form computes, and so are the accumulator
+// and the verdict. (s = 0 there gives w = 0 and the point at infinity: false
+// too.)
+CMTV_HD void secp_batch_s(scn& s, bool active) {
+  const bool one = !active || scn_is_zero(s);
+#pragma unroll
+  for (int i = 0; i < 8; i++) s.v[i] = one ? (i == 0 ? 1u : 0u) : s.v[i];
+}
+
+template <int KB, class Src, class Pre, class GTab>
+CMTV_HD void secp_verify_keyed_batch_lane(Src& src, Pre& pre, const GTab& gt) {
+  uint32_t okbits = 0;
+  scn prod;
+#pragma unroll 1
+  for (int r = 0; r < KB; r++) {
+    scn rr, s;
+    const bool active = src.active(r);
+    const bool ok = secp_sig_scalars(rr, s, src.sig(r)) && active;
+    okbits |= (ok ? 1u : 0u) << r;
+    secp_batch_s(s, active);
+    if (r == 0)
+      prod = s;
+    else
+      scn_mul(prod, prod, s);
+    pre.store(r, prod);
+  }
+  scn inv;
+  scn_invert(inv, prod);
+#pragma unroll 1
+  for (int r = KB - 1; r >= 0; r--) {
+    scn rr, s, w;
+    (void)secp_sig_scalars(rr, s, src.sig(r));
+    secp_batch_s(s, src.active(r));
+    if (r > 0) {
+      scn before;
+      pre.load(r - 1, before);
+      scn_mul(w, inv, before);  // 1 / s_r
+      scn_mul(inv, inv, s);     // 1 / (s_0 ... s_{r-1})
+    } else {
+      w = inv;
+    }
+    typename Src::QTab qt;
+    const bool key_ok = src.key(r, qt);
+    const uint8_t* msg;
+    const uint32_t ml = src.message(r, msg);
+    scn e, u1, u2;
+    secp_msg_scalar(e, msg, ml);
+    secp_u1_u2(u1, u2, e, rr, w);
+    pt256 acc;
+    pt_set_infinity(acc);
+    secp_comb_add(acc, u1, gt);
+    secp_comb_add(acc, u2, qt);
+    src.verdict(r, secp_x_is_r(acc, rr) && key_ok && ((okbits >> r) & 1u) != 0);
+  }
 }
 
 }  // namespace cmtv

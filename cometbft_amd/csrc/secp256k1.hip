@@ -19,6 +19,10 @@
 //     commit signature written from the commit's template (kernels.h SbFuse,
 //     signbytes.h sb_write) into the lane's own LDS slot of kSbFuseMaxMsg
 //     bytes and hashed from there, so a commit ships no message buffer.
+//   k_verify_secp256k1_keyed_batch<KB>: the keyed templated kernel with KB =
+//     4 or 8 signatures per lane sharing one inversion mod n (Montgomery's
+//     trick); the lane's running products go through the launch's scratch.
+//     Launched for cross-height typed batches only (commits_typed.cpp).
 //
 // Memory layout: pk n x 33 B and sig n x 64 B (read bytewise: a 33-byte
 // stride has no alignment), msg flat bytes + (n+1) u32 offsets as the other
@@ -212,6 +216,104 @@ __global__ __launch_bounds__(64) void k_verify_secp256k1_keyed_tmpl(uint32_t n, 
   bool v = secp_verify_keyed_tmpl_one(in_set && key_ok[key] != 0, sig + 64 * (size_t)i, out, slot, m.tp, sb.blob,
                                       m.flag, m.sec, m.nanos, qt, gt);
   lane_verdict_store(gid, active, v, out_valid, out_bitmap);
+}
+
+// The batch kernel's running products in the launch's scratch, word-major /
+// lane-minor like the per-lane table above: word w of round r for lane l at
+// (r * 8 + w) * lanes + l, a wave's access to one word is one 256-byte line.
+struct DevSecpPre {
+  uint32_t* __restrict__ base;
+  uint32_t lanes;
+  uint32_t lane;
+  __device__ __forceinline__ void store(int r, const scn& x) {
+    uint32_t* q = base + (size_t)(r * 8) * lanes + lane;
+#pragma unroll
+    for (int i = 0; i < 8; i++) q[(size_t)i * lanes] = x.v[i];
+  }
+  __device__ __forceinline__ void load(int r, scn& x) const {
+    const uint32_t* q = base + (size_t)(r * 8) * lanes + lane;
+#pragma unroll
+    for (int i = 0; i < 8; i++) x.v[i] = q[(size_t)i * lanes];
+  }
+};
+
+// A lane's rounds of k_verify_secp256k1_keyed_batch (secp256k1.h
+// secp_verify_keyed_batch_lane Src): round r is signature gid + r * lanes; a
+// round past n takes signature n - 1 and writes nothing.
+struct DevSecpBatchSrc {
+  using QTab = DevSecpGTab;
+  uint32_t n, n_keys, lanes, gid;
+  const uint32_t* __restrict__ key_idx;
+  const uint8_t* __restrict__ key_ok;
+  const uint32_t* __restrict__ qtab;
+  const uint8_t* __restrict__ sigs;
+  const SbFuse& sb;
+  uint8_t* slot;
+  uint8_t* __restrict__ out_valid;
+  uint64_t* __restrict__ out_bitmap;
+  __device__ __forceinline__ uint32_t at(int r) const { return gid + (uint32_t)r * lanes; }
+  __device__ __forceinline__ bool active(int r) const { return at(r) < n; }
+  __device__ __forceinline__ uint32_t index(int r) const { return active(r) ? at(r) : n - 1; }
+  __device__ __forceinline__ const uint8_t* sig(int r) const { return sigs + 64 * (size_t)index(r); }
+  __device__ __forceinline__ bool key(int r, QTab& qt) const {
+    const uint32_t k = key_idx[index(r)];
+    const bool in_set = k < n_keys;
+    const uint32_t key = in_set ? k : 0;
+    qt.rows = qtab + (size_t)key * kSecpGtabWords;
+    return in_set && key_ok[key] != 0;
+  }
+  __device__ __forceinline__ uint32_t message(int r, const uint8_t*& msg) const {
+    const SecpLaneMsg m(sb, index(r));
+    LdsBytes out{slot};
+    msg = slot;
+    return sb_write(out, m.tp, sb.blob, m.flag, m.sec, m.nanos);
+  }
+  __device__ __forceinline__ void verdict(int r, bool v) const {
+    // a wave whose 64 signatures of this round are all past n has no bitmap word
+    if (at(r) - threadIdx.x < n) lane_verdict_store(at(r), active(r), v, out_valid, out_bitmap);
+  }
+};
+
+// k_verify_secp256k1_keyed_tmpl with KB signatures per lane sharing one
+// inversion mod n (secp256k1.h secp_verify_keyed_batch_lane): signature
+// s = gid + r * lanes in round r, so every round of a wave covers 64
+// consecutive signatures and one bitmap word; ceil(n / (64 KB)) workgroups.
+// pre: lanes x KB x 8 words of scratch. Verdicts equal the per-lane kernel's.
+template <int KB>
+__global__ __launch_bounds__(64) void k_verify_secp256k1_keyed_batch(uint32_t n, uint32_t n_keys,
+                                                                     const uint32_t* __restrict__ key_idx,
+                                                                     const uint8_t* __restrict__ key_ok,
+                                                                     const uint32_t* __restrict__ qtab,
+                                                                     const uint8_t* __restrict__ sig, SbFuse sb,
+                                                                     const uint32_t* __restrict__ gtab,
+                                                                     uint32_t* __restrict__ pre,
+                                                                     uint8_t* __restrict__ out_valid,
+                                                                     uint64_t* __restrict__ out_bitmap) {
+  __shared__ uint32_t slots[64][kSbFuseMaxMsg / 4];
+  const uint32_t lanes = gridDim.x * 64u, gid = blockIdx.x * 64u + threadIdx.x;
+  DevSecpBatchSrc src{n,  n_keys, lanes, gid, key_idx, key_ok, qtab, sig, sb, reinterpret_cast<uint8_t*>(slots[threadIdx.x]),
+                      out_valid, out_bitmap};
+  DevSecpPre pr{pre, lanes, gid};
+  DevSecpGTab gt{gtab};
+  secp_verify_keyed_batch_lane<KB>(src, pr, gt);
+}
+
+hipError_t launch_verify_secp256k1_keyed_batch(uint32_t kb, uint32_t n, uint32_t n_keys, const uint32_t* key_idx,
+                                               const uint8_t* key_ok, const uint32_t* qtab, const void* sig,
+                                               const SbFuse& sb, const uint32_t* gtab, uint32_t* pre, void* valid,
+                                               void* bitmap, hipStream_t s) {
+  if (n == 0) return hipSuccess;
+  if (!sb.tmpls || !pre || (kb != 4 && kb != 8)) return hipErrorInvalidValue;
+  const dim3 grid((n + 64 * kb - 1) / (64 * kb)), block(64);
+  if (kb == 8)
+    hipLaunchKernelGGL(k_verify_secp256k1_keyed_batch<8>, grid, block, 0, s, n, n_keys, key_idx, key_ok, qtab,
+                       static_cast<const uint8_t*>(sig), sb, gtab, pre, static_cast<uint8_t*>(valid),
+                       static_cast<uint64_t*>(bitmap));
+  else
+    hipLaunchKernelGGL(k_verify_secp256k1_keyed_batch<4>, grid, block, 0, s, n, n_keys, key_idx, key_ok, qtab,
+                       static_cast<const uint8_t*>(sig), sb, gtab, pre, static_cast<uint8_t*>(valid),
+                       static_cast<uint64_t*>(bitmap));
+  return hipGetLastError();
 }
 
 hipError_t launch_verify_secp256k1_tmpl(uint32_t n, const void* pk, const void* sig, const SbFuse& sb,

@@ -322,9 +322,10 @@ def _error_for(rc, res, msg):
 
 def verify_commits(kind: int, chain_id: str, items, ctx: Context | None = None, mode: int = MODE_GO_STDLIB,
                    trust_level=(1, 3)):
-    """Cross-height batching (cmtv_verify_commits): items is a sequence of
-    (ValidatorSet, BlockID | None, height, Commit). All their signatures go to
-    the device in ONE batch; returns, per item, None (the reference's nil) or
+    """Cross-height batching (cmtv_verify_commits; cmtv_verify_commits_typed
+    when a validator of any item holds a secp256k1 or sr25519 key): items is a
+    sequence of (ValidatorSet, BlockID | None, height, Commit). All their
+    signatures go to the device in ONE batch per key type; returns, per item, None (the reference's nil) or
     the exception its VerifyCommit* would have returned -- not raised, so one
     bad height does not hide the others."""
     if len(items) == 0:
@@ -352,10 +353,16 @@ class PackedCommits:
         cm_arr = (N.cmtv_commit * n)()
         bid_arr = (N.cmtv_block_id * n)()
         heights = (ctypes.c_int64 * n)()
+        # one CMTV_KEY_* array per set that is not all Ed25519, else NULL
+        kt_arr = (ctypes.POINTER(ctypes.c_uint8) * n)()
+        typed = False
         for c, (vals, block_id, height, commit) in enumerate(items):
             vs, kv = vals._pack()
             cm, kc = _pack_commit(commit, arena)
             vs_arr[c], cm_arr[c] = vs, cm
+            if kv[5][:-1].any():
+                kt_arr[c] = _p8(kv[5])
+                typed = True
             keep += [kv, kc]
             if block_id is not None:
                 bid, kb = block_id._c()
@@ -367,15 +374,22 @@ class PackedCommits:
         self.num, self.den = trust_level if kind == N.VERIFY_COMMIT_LIGHT_TRUSTING else (0, 0)
         self.vs_arr, self.cm_arr, self.heights, self._keep = vs_arr, cm_arr, heights, keep
         self.bid_arr = bid_arr if kind != N.VERIFY_COMMIT_LIGHT_TRUSTING else None
+        self.kt_arr = kt_arr if typed else None
         self.res = (N.cmtv_commit_result * n)()
         self.rcs = (ctypes.c_int * n)()
         self.bufs = ctypes.create_string_buffer(n * self.cap)
 
     def call(self, ctx: Context) -> None:
-        """The C call alone (results left in res / rcs / bufs)."""
-        rc = N.lib().cmtv_verify_commits(ctx.handle, self.kind, self.mode, self.cid, len(self.cid), self.n,
-                                         self.vs_arr, self.bid_arr, self.heights, self.cm_arr, self.num, self.den,
-                                         self.res, self.rcs, self.bufs, self.cap)
+        """The C call alone (results left in res / rcs / bufs): the typed
+        entry point when a validator of any item is not Ed25519."""
+        if self.kt_arr is not None:
+            rc = N.lib().cmtv_verify_commits_typed(ctx.handle, self.kind, self.mode, self.cid, len(self.cid), self.n,
+                                                   self.vs_arr, self.kt_arr, self.bid_arr, self.heights, self.cm_arr,
+                                                   self.num, self.den, self.res, self.rcs, self.bufs, self.cap)
+        else:
+            rc = N.lib().cmtv_verify_commits(ctx.handle, self.kind, self.mode, self.cid, len(self.cid), self.n,
+                                             self.vs_arr, self.bid_arr, self.heights, self.cm_arr, self.num, self.den,
+                                             self.res, self.rcs, self.bufs, self.cap)
         N.check(rc, "cmtv_verify_commits")
 
     def verify(self, ctx: Context):

@@ -100,7 +100,10 @@ typedef struct cmtv_stats {
                               waiting for the hash helper and hashed their own
                               signatures (timing only, never a verdict)  */
   uint32_t live_devices;     /* devices still taking work                 */
-  uint32_t reserved;
+  uint32_t secp_batch_launches; /* launches of the secp256k1 kernel that
+                              shares one inversion mod n among 4 or 8
+                              signatures of a lane (cross-height typed
+                              batches, cmtv_verify_commits_typed); wraps  */
   uint64_t timed_calls;      /* calls whose kernel time device_ms holds   */
   uint64_t rccl_failures;    /* RCCL all-gathers that failed; that gather
                               and every later one of the context used peer
@@ -554,8 +557,8 @@ int cmtv_verify_commit(cmtv_ctx* ctx, uint32_t kind, uint32_t mode, const char* 
  * its first call (528 KiB per key on the first device) and later calls use
  * the registered-key kernel; mixed sets use key bytes. A typed call never
  * enters the cross-height pipeline or the speculative path, and its Ed25519
- * and secp256k1 parts do not consult cmtv_verdict_cache. Cross-height typed
- * batching is out of scope: cmtv_verify_commits has no typed form. */
+ * and secp256k1 parts do not consult cmtv_verdict_cache. Many heights in one
+ * call: cmtv_verify_commits_typed below. */
 enum { CMTV_KEY_ED25519 = 0, CMTV_KEY_SECP256K1 = 1, CMTV_KEY_SR25519 = 2 };
 int cmtv_verify_commit_typed(cmtv_ctx* ctx, uint32_t kind, uint32_t mode, const char* chain_id, size_t chain_id_len,
                              const cmtv_valset* vals, const uint8_t* key_types, const cmtv_block_id* block_id,
@@ -575,6 +578,38 @@ int cmtv_verify_commits(cmtv_ctx* ctx, uint32_t kind, uint32_t mode, const char*
                         size_t n, const cmtv_valset* vals, const cmtv_block_id* block_ids, const int64_t* heights,
                         const cmtv_commit* commits, uint64_t trust_num, uint64_t trust_den,
                         cmtv_commit_result* results, int* rcs, char* msg_bufs, size_t msg_cap);
+
+/* cmtv_verify_commits for typed validator sets: per commit i the outcome --
+ * rcs[i], results[i] and the string at msg_bufs + i * msg_cap -- equals
+ * cmtv_verify_commit_typed(ctx, kind, mode, chain_id, &vals[i], key_types[i],
+ * &block_ids[i], heights[i], &commits[i], ...). key_types[i] is NULL (every
+ * key of vals[i] is Ed25519) or vals[i].n_vals bytes of CMTV_KEY_*; the array
+ * itself may be NULL. A type above CMTV_KEY_SR25519 or a 65-byte secp256k1
+ * key anywhere is CMTV_EINVAL for the call; the return value is
+ * cmtv_verify_commits'. When no validator of any commit is non-Ed25519 the
+ * call IS cmtv_verify_commits (same code, pipeline included, same bytes out).
+ * Otherwise the planned signatures of all commits are split by key type and
+ * each share goes to the device in as few batches as its limits allow (the
+ * sign-bytes of one batch stay below 2 GiB): Ed25519 and secp256k1 with their
+ * CanonicalVotes built on the device from one template per commit, sr25519
+ * with sign-bytes encoded on the host. A commit that fails its preamble costs
+ * no device work. With cmtv_keyset_cache on, consecutive commits whose sets
+ * are all secp256k1 (keys packed at 33 bytes) and hold the same keys form one
+ * group verified by registered keys in one batch; groups run one after
+ * another, so a call may hold more distinct sets than the cache. Launches of
+ * such a group that are large enough share one inversion mod n among the 4
+ * or 8 signatures of a lane (cmtv_stats.secp_batch_launches counts them;
+ * CMTV_KEYED_BATCH_MIN_WAVES sets the size, as for the Ed25519 form), with
+ * verdicts bit-identical to the one-signature-per-lane kernel's. Mixed sets
+ * use key bytes. Out of scope for typed calls: the cross-height pipeline and
+ * its pinned-arena direct chunks, the verdict cache, multi-device sharding
+ * (secp256k1 runs on the context's first device) and a templated sr25519
+ * kernel. */
+int cmtv_verify_commits_typed(cmtv_ctx* ctx, uint32_t kind, uint32_t mode, const char* chain_id, size_t chain_id_len,
+                              size_t n, const cmtv_valset* vals, const uint8_t* const* key_types,
+                              const cmtv_block_id* block_ids, const int64_t* heights, const cmtv_commit* commits,
+                              uint64_t trust_num, uint64_t trust_den, cmtv_commit_result* results, int* rcs,
+                              char* msg_bufs, size_t msg_cap);
 
 /* Pinned host memory for the caller's argument arena (the
  * zero-copy boundary). A cgo shim that builds its cmtv_verify_commits
