@@ -670,75 +670,54 @@ int stage_sigs_early_locked(cmtv_ctx* ctx, const uint8_t* sigs, size_t n, const 
   return CMTV_OK;
 }
 
-// Host buffers in, verdicts out, on devs[0] (caller holds the context lock):
-// one staging block pk | sig | off | msg, the verdict bitmap back.
-int verify_secp_host_locked(cmtv_ctx* ctx, size_t n, const uint8_t* pk, const uint8_t* sig,
-                                   const uint8_t* msg, const uint32_t* msg_off, uint8_t* out_valid,
-                                   uint64_t* out_bitmap) {
-  CmtvDev& D = ctx->devs[0];
-  const size_t msg_bytes = msg_off[n];
-  const size_t o_sig = align_up(33 * n, 16), o_off = o_sig + 64 * n, o_msg = o_off + 4 * (n + 1);
-  const size_t words = (n + 63) / 64;
-  hipError_t e;
-  // +4: the kernel's aligned reads end inside the last message byte's word
-  if ((e = D.secp_in.ensure(o_msg + msg_bytes + 4)) != hipSuccess) return hip_fail(e);
-  if ((e = D.secp_out.ensure(8 * words)) != hipSuccess) return hip_fail(e);
-  auto* din = static_cast<uint8_t*>(D.secp_in.p);
+// What every secp256k1 host batch does once its inputs are on their way to
+// D.secp_in on D.stream: the launch (enqueue(bitmap, stream)), the verdict
+// bitmap back, the wait for it.
+template <class Enqueue>
+static int secp_finish(cmtv_ctx* ctx, CmtvDev& D, size_t n, uint8_t* out_valid, uint64_t* out_bitmap, Enqueue enqueue) {
   hipStream_t s = D.stream;
-  if ((e = hipMemcpyAsync(din, pk, 33 * n, hipMemcpyHostToDevice, s)) != hipSuccess) return hip_fail(e);
-  if ((e = hipMemcpyAsync(din + o_sig, sig, 64 * n, hipMemcpyHostToDevice, s)) != hipSuccess) return hip_fail(e);
-  if ((e = hipMemcpyAsync(din + o_off, msg_off, 4 * (n + 1), hipMemcpyHostToDevice, s)) != hipSuccess)
-    return hip_fail(e);
-  if (msg_bytes && (e = hipMemcpyAsync(din + o_msg, msg, msg_bytes, hipMemcpyHostToDevice, s)) != hipSuccess)
-    return hip_fail(e);
   auto* dbm = static_cast<uint64_t*>(D.secp_out.p);
-  const int rc = enqueue_verify_secp(ctx, D, n, din, din + o_sig, din + o_msg,
-                                     reinterpret_cast<const uint32_t*>(din + o_off), nullptr, dbm, s);
+  const int rc = enqueue(dbm, s);
   if (rc != CMTV_OK) {
-    (void)hipStreamSynchronize(s);  // the copies read the caller's buffers
+    (void)hipStreamSynchronize(s);  // the copies read the caller's buffers (or the staging)
     return rc;
   }
-  std::vector<uint64_t> bm(words);
-  if ((e = hipMemcpyAsync(bm.data(), dbm, 8 * words, hipMemcpyDeviceToHost, s)) != hipSuccess) return hip_fail(e);
+  std::vector<uint64_t> bm((n + 63) / 64);
+  hipError_t e;
+  if ((e = hipMemcpyAsync(bm.data(), dbm, 8 * bm.size(), hipMemcpyDeviceToHost, s)) != hipSuccess) return hip_fail(e);
   if ((e = wait_stream(ctx, s)) != hipSuccess) return hip_fail(e);
   // (the kernel's ballot words hold 0 for the lanes past n: the mask changes nothing)
   ctx->stats.invalid += bitmap_tail(bm.data(), n, out_bitmap, out_valid);
   return CMTV_OK;
 }
 
-// The same by registered keys: key_idx | sig | off | msg (the caller has
+// Host buffers in, verdicts out, on devs[0] (caller holds the context lock):
+// one staging block keys | sig | off | msg, the verdict bitmap back. keys: n x
+// 33 key bytes, or with ks n u32 indices of registered keys (the caller has
 // checked every index against the key set).
-int verify_secp_keyed_host_locked(cmtv_ctx* ctx, const cmtv_secp_keyset* ks, size_t n, const uint32_t* key_idx,
-                                  const uint8_t* sig, const uint8_t* msg, const uint32_t* msg_off, uint8_t* out_valid,
-                                  uint64_t* out_bitmap) {
+int verify_secp_host_locked(cmtv_ctx* ctx, const cmtv_secp_keyset* ks, size_t n, const void* keys, const uint8_t* sig,
+                            const uint8_t* msg, const uint32_t* msg_off, uint8_t* out_valid, uint64_t* out_bitmap) {
   CmtvDev& D = ctx->devs[0];
-  const size_t msg_bytes = msg_off[n];
-  const size_t o_sig = align_up(4 * n, 16), o_off = o_sig + 64 * n, o_msg = o_off + 4 * (n + 1);
-  const size_t words = (n + 63) / 64;
+  const size_t msg_bytes = msg_off[n], key_bytes = (ks ? 4 : 33) * n;
+  const size_t o_sig = align_up(key_bytes, 16), o_off = o_sig + 64 * n, o_msg = o_off + 4 * (n + 1);
   hipError_t e;
   // +4: the kernel's aligned reads end inside the last message byte's word
   if ((e = D.secp_in.ensure(o_msg + msg_bytes + 4)) != hipSuccess) return hip_fail(e);
-  if ((e = D.secp_out.ensure(8 * words)) != hipSuccess) return hip_fail(e);
+  if ((e = D.secp_out.ensure(8 * ((n + 63) / 64))) != hipSuccess) return hip_fail(e);
   auto* din = static_cast<uint8_t*>(D.secp_in.p);
   hipStream_t s = D.stream;
-  if ((e = hipMemcpyAsync(din, key_idx, 4 * n, hipMemcpyHostToDevice, s)) != hipSuccess) return hip_fail(e);
+  if ((e = hipMemcpyAsync(din, keys, key_bytes, hipMemcpyHostToDevice, s)) != hipSuccess) return hip_fail(e);
   if ((e = hipMemcpyAsync(din + o_sig, sig, 64 * n, hipMemcpyHostToDevice, s)) != hipSuccess) return hip_fail(e);
   if ((e = hipMemcpyAsync(din + o_off, msg_off, 4 * (n + 1), hipMemcpyHostToDevice, s)) != hipSuccess)
     return hip_fail(e);
   if (msg_bytes && (e = hipMemcpyAsync(din + o_msg, msg, msg_bytes, hipMemcpyHostToDevice, s)) != hipSuccess)
     return hip_fail(e);
-  auto* dbm = static_cast<uint64_t*>(D.secp_out.p);
-  const int rc = enqueue_verify_secp_keyed(ctx, D, ks, n, reinterpret_cast<const uint32_t*>(din), din + o_sig,
-                                           din + o_msg, reinterpret_cast<const uint32_t*>(din + o_off), nullptr, dbm, s);
-  if (rc != CMTV_OK) {
-    (void)hipStreamSynchronize(s);  // the copies read the caller's buffers
-    return rc;
-  }
-  std::vector<uint64_t> bm(words);
-  if ((e = hipMemcpyAsync(bm.data(), dbm, 8 * words, hipMemcpyDeviceToHost, s)) != hipSuccess) return hip_fail(e);
-  if ((e = wait_stream(ctx, s)) != hipSuccess) return hip_fail(e);
-  ctx->stats.invalid += bitmap_tail(bm.data(), n, out_bitmap, out_valid);
-  return CMTV_OK;
+  const auto* d_off = reinterpret_cast<const uint32_t*>(din + o_off);
+  return secp_finish(ctx, D, n, out_valid, out_bitmap, [&](uint64_t* dbm, hipStream_t st) {
+    return ks ? enqueue_verify_secp_keyed(ctx, D, ks, n, reinterpret_cast<const uint32_t*>(din), din + o_sig,
+                                          din + o_msg, d_off, nullptr, dbm, st)
+              : enqueue_verify_secp(ctx, D, n, din, din + o_sig, din + o_msg, d_off, nullptr, dbm, st);
+  });
 }
 
 // Commit signatures over secp256k1 keys with templated sign-bytes
@@ -747,26 +726,27 @@ int verify_secp_keyed_host_locked(cmtv_ctx* ctx, const cmtv_secp_keyset* ks, siz
 //   (n + 1, non-fused only) | templates | sig | pk (n x 33) | flag | blob
 // with the 8-byte array first and the 4-byte ones next, so every array the
 // kernels read as int64 / int32 is aligned whatever n is; on the device the
-// non-fused route's messages follow it. bulk: the fused registered-key route
-// may take the batched kernel (launch.cpp enqueue_verify_secp_keyed).
-static int secp_templated(cmtv_ctx* ctx, size_t n, const uint8_t* pk33, const cmtv_secp_keyset* ks,
-                          const uint32_t* key_idx, const uint8_t* sig, const void* tmpls, size_t n_tmpls,
-                          const uint8_t* blob, size_t blob_len, const uint32_t* tidx, const uint8_t* commit_flag,
-                          const int64_t* sec, const int32_t* nanos, uint8_t* out_valid, bool bulk) {
+// non-fused route's messages follow it. r.bulk: the fused registered-key
+// route may take the batched kernel (launch.cpp enqueue_verify_secp_keyed).
+int verify_secp_templated_locked(cmtv_ctx* ctx, const SecpTemplated& r, uint8_t* out_valid) {
+  const size_t n = r.n, n_tmpls = r.n_tmpls, blob_len = r.blob_len;
+  const cmtv_secp_keyset* ks = r.ks;
+  const uint32_t* tidx = r.tidx;
   if (n == 0) return CMTV_OK;
-  if (!sig || !tmpls || !n_tmpls || !commit_flag || !sec || !nanos || (ks ? !key_idx : !pk33)) return CMTV_EINVAL;
+  if (!r.sig || !r.tmpls || !n_tmpls || !r.commit_flag || !r.sec || !r.nanos || (ks ? !r.key_idx : !r.pk33))
+    return CMTV_EINVAL;
   if (ctx->devs.empty() || ctx->devs[0].failed) return CMTV_ENODEV;
   CmtvDev& D = ctx->devs[0];
   (void)hipSetDevice(D.ordinal);
-  const auto* tp = static_cast<const SbTemplate*>(tmpls);
+  const auto* tp = static_cast<const SbTemplate*>(r.tmpls);
   // message lengths: they decide the route, and give the non-fused route's offsets
   uint32_t max_len = 0;
   uint64_t total = 0;
   for (size_t i = 0; i < n; i++) {
     const uint32_t ti = tidx ? tidx[i] : 0u;
     if (ti >= n_tmpls) return CMTV_EINVAL;
-    if (ks && key_idx[i] >= ks->n) return CMTV_EINVAL;
-    const uint32_t len = sb_msg_len(tp[ti], commit_flag[i] != 0, sec[i], nanos[i]);
+    if (ks && r.key_idx[i] >= ks->n) return CMTV_EINVAL;
+    const uint32_t len = sb_msg_len(tp[ti], r.commit_flag[i] != 0, r.sec[i], r.nanos[i]);
     max_len = std::max(max_len, len);
     total += len;
   }
@@ -781,35 +761,33 @@ static int secp_templated(cmtv_ctx* ctx, size_t n, const uint8_t* pk33, const cm
   const size_t in_bytes = align_up(o_blob + blob_len + 16, 16);
   // k_sign_bytes writes 16 zero bytes after the last message
   const size_t o_msg = in_bytes, dev_bytes = fuse ? in_bytes : align_up(o_msg + total + 16 + 4, 16);
-  const size_t words = (n + 63) / 64;
   hipError_t e;
   if ((e = D.secp_in.ensure(dev_bytes)) != hipSuccess) return hip_fail(e);
-  if ((e = D.secp_out.ensure(8 * words)) != hipSuccess) return hip_fail(e);
+  if ((e = D.secp_out.ensure(8 * ((n + 63) / 64))) != hipSuccess) return hip_fail(e);
   if (D.secp_stage.size() < in_bytes) D.secp_stage.resize(in_bytes);
   uint8_t* h = D.secp_stage.data();
-  std::memcpy(h + o_sec, sec, 8 * n);
-  std::memcpy(h + o_nanos, nanos, 4 * n);
+  std::memcpy(h + o_sec, r.sec, 8 * n);
+  std::memcpy(h + o_nanos, r.nanos, 4 * n);
   if (tidx)
     std::memcpy(h + o_tidx, tidx, 4 * n);
   else
     std::memset(h + o_tidx, 0, 4 * n);
-  if (ks) std::memcpy(h + o_kidx, key_idx, 4 * n);
+  if (ks) std::memcpy(h + o_kidx, r.key_idx, 4 * n);
   if (!fuse) {
     uint32_t o = 0;
     for (size_t i = 0; i <= n; i++) {
       std::memcpy(h + o_off + 4 * i, &o, 4);
-      if (i < n) o += sb_msg_len(tp[tidx ? tidx[i] : 0u], commit_flag[i] != 0, sec[i], nanos[i]);
+      if (i < n) o += sb_msg_len(tp[tidx ? tidx[i] : 0u], r.commit_flag[i] != 0, r.sec[i], r.nanos[i]);
     }
   }
-  std::memcpy(h + o_tmpl, tmpls, tb);
-  std::memcpy(h + o_sig, sig, 64 * n);
-  if (!ks) std::memcpy(h + o_pk, pk33, 33 * n);
-  std::memcpy(h + o_flag, commit_flag, n);
-  if (blob_len) std::memcpy(h + o_blob, blob, blob_len);
+  std::memcpy(h + o_tmpl, r.tmpls, tb);
+  std::memcpy(h + o_sig, r.sig, 64 * n);
+  if (!ks) std::memcpy(h + o_pk, r.pk33, 33 * n);
+  std::memcpy(h + o_flag, r.commit_flag, n);
+  if (blob_len) std::memcpy(h + o_blob, r.blob, blob_len);
   std::memset(h + o_blob + blob_len, 0, in_bytes - o_blob - blob_len);
   auto* din = static_cast<uint8_t*>(D.secp_in.p);
-  hipStream_t s = D.stream;
-  if ((e = hipMemcpyAsync(din, h, in_bytes, hipMemcpyHostToDevice, s)) != hipSuccess) return hip_fail(e);
+  if ((e = hipMemcpyAsync(din, h, in_bytes, hipMemcpyHostToDevice, D.stream)) != hipSuccess) return hip_fail(e);
   SbFuse sb;
   sb.tmpls = din + o_tmpl;
   sb.blob = din + o_blob;
@@ -817,37 +795,11 @@ static int secp_templated(cmtv_ctx* ctx, size_t n, const uint8_t* pk33, const cm
   sb.flag = din + o_flag;
   sb.sec = reinterpret_cast<const int64_t*>(din + o_sec);
   sb.nanos = reinterpret_cast<const int32_t*>(din + o_nanos);
-  auto* dbm = static_cast<uint64_t*>(D.secp_out.p);
-  const int rc = enqueue_verify_secp_templated(ctx, D, n, din + o_pk, ks, reinterpret_cast<const uint32_t*>(din + o_kidx),
-                                               din + o_sig, sb, max_len, reinterpret_cast<const uint32_t*>(din + o_off),
-                                               din + o_msg, nullptr, dbm, s, bulk);
-  if (rc != CMTV_OK) {
-    (void)hipStreamSynchronize(s);  // the copy reads the staging
-    return rc;
-  }
-  std::vector<uint64_t> bm(words);
-  if ((e = hipMemcpyAsync(bm.data(), dbm, 8 * words, hipMemcpyDeviceToHost, s)) != hipSuccess) return hip_fail(e);
-  if ((e = wait_stream(ctx, s)) != hipSuccess) return hip_fail(e);
-  ctx->stats.invalid += bitmap_tail(bm.data(), n, nullptr, out_valid);
-  return CMTV_OK;
-}
-
-int verify_secp_templated_locked(cmtv_ctx* ctx, size_t n, const uint8_t* pk33, const cmtv_secp_keyset* ks,
-                                 const uint32_t* key_idx, const uint8_t* sig, const void* tmpls, size_t n_tmpls,
-                                 const uint8_t* blob, size_t blob_len, const uint32_t* tidx,
-                                 const uint8_t* commit_flag, const int64_t* sec, const int32_t* nanos,
-                                 uint8_t* out_valid) {
-  return secp_templated(ctx, n, pk33, ks, key_idx, sig, tmpls, n_tmpls, blob, blob_len, tidx, commit_flag, sec, nanos,
-                        out_valid, false);
-}
-
-int verify_secp_templated_bulk_locked(cmtv_ctx* ctx, size_t n, const uint8_t* pk33, const cmtv_secp_keyset* ks,
-                                      const uint32_t* key_idx, const uint8_t* sig, const void* tmpls, size_t n_tmpls,
-                                      const uint8_t* blob, size_t blob_len, const uint32_t* tidx,
-                                      const uint8_t* commit_flag, const int64_t* sec, const int32_t* nanos,
-                                      uint8_t* out_valid) {
-  return secp_templated(ctx, n, pk33, ks, key_idx, sig, tmpls, n_tmpls, blob, blob_len, tidx, commit_flag, sec, nanos,
-                        out_valid, true);
+  return secp_finish(ctx, D, n, out_valid, nullptr, [&](uint64_t* dbm, hipStream_t s) {
+    return enqueue_verify_secp_templated(ctx, D, n, din + o_pk, ks, reinterpret_cast<const uint32_t*>(din + o_kidx),
+                                         din + o_sig, sb, max_len, reinterpret_cast<const uint32_t*>(din + o_off),
+                                         din + o_msg, nullptr, dbm, s, r.bulk);
+  });
 }
 
 }  // namespace cmtv

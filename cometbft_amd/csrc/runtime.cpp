@@ -616,7 +616,7 @@ int cmtv_verify_secp256k1(cmtv_ctx* ctx, size_t n, const uint8_t* pk, const uint
   if (!host_args_ok(ctx, 0, n, pk, sig, msg, msg_off, out_valid, out_bitmap)) return CMTV_EINVAL;
   if (n == 0) return CMTV_OK;
   return on_dev0(ctx, [&](CmtvDev&) {
-    return verify_secp_host_locked(ctx, n, pk, sig, msg, msg_off, out_valid, out_bitmap);
+    return verify_secp_host_locked(ctx, nullptr, n, pk, sig, msg, msg_off, out_valid, out_bitmap);
   });
 }
 
@@ -668,7 +668,7 @@ int cmtv_verify_secp256k1_indexed(cmtv_ctx* ctx, const cmtv_secp_keyset* ks, siz
   for (size_t i = 0; i < n; i++)
     if (key_idx[i] >= ks->n) return CMTV_EINVAL;
   return on_dev0(ctx, [&](CmtvDev&) {
-    return verify_secp_keyed_host_locked(ctx, ks, n, key_idx, sig, msg, msg_off, out_valid, out_bitmap);
+    return verify_secp_host_locked(ctx, ks, n, key_idx, sig, msg, msg_off, out_valid, out_bitmap);
   });
 }
 

@@ -58,22 +58,28 @@ int verify_templated_locked(cmtv_ctx* ctx, size_t n, const uint8_t* pk, const ui
 // messages themselves when every one fits kSbFuseMaxMsg bytes, else
 // k_sign_bytes writes them first. Verdict bytes back, the call waits for them
 // (as cmtv_verify_secp256k1). tidx null: every signature uses template 0.
-// Caller holds the context lock.
-int verify_secp_templated_locked(cmtv_ctx* ctx, size_t n, const uint8_t* pk33, const cmtv_secp_keyset* ks,
-                                 const uint32_t* key_idx, const uint8_t* sig, const void* tmpls, size_t n_tmpls,
-                                 const uint8_t* blob, size_t blob_len, const uint32_t* tidx,
-                                 const uint8_t* commit_flag, const int64_t* sec, const int32_t* nanos,
-                                 uint8_t* out_valid);
-// The same for the signatures of many commits (commits_typed.cpp): with
-// registered keys and fused sign-bytes the launches may take KB signatures
-// per lane sharing one inversion mod n (k_verify_secp256k1_keyed_batch) when
-// they are large enough for it (CMTV_KEYED_BATCH_MIN_WAVES); every other
-// route, and every verdict, is verify_secp_templated_locked's.
-int verify_secp_templated_bulk_locked(cmtv_ctx* ctx, size_t n, const uint8_t* pk33, const cmtv_secp_keyset* ks,
-                                      const uint32_t* key_idx, const uint8_t* sig, const void* tmpls, size_t n_tmpls,
-                                      const uint8_t* blob, size_t blob_len, const uint32_t* tidx,
-                                      const uint8_t* commit_flag, const int64_t* sec, const int32_t* nanos,
-                                      uint8_t* out_valid);
+// bulk (the signatures of many commits): with registered keys and fused
+// sign-bytes the launches may take KB signatures per lane sharing one
+// inversion mod n (k_verify_secp256k1_keyed_batch) when they are large
+// enough for it (CMTV_KEYED_BATCH_MIN_WAVES); every other route, and every
+// verdict, is the same. Caller holds the context lock.
+struct SecpTemplated {
+  size_t n;
+  const uint8_t* pk33;
+  const cmtv_secp_keyset* ks;
+  const uint32_t* key_idx;
+  const uint8_t* sig;
+  const void* tmpls;
+  size_t n_tmpls;
+  const uint8_t* blob;
+  size_t blob_len;
+  const uint32_t* tidx;
+  const uint8_t* commit_flag;
+  const int64_t* sec;
+  const int32_t* nanos;
+  bool bulk = false;
+};
+int verify_secp_templated_locked(cmtv_ctx* ctx, const SecpTemplated& r, uint8_t* out_valid);
 // cmtv_keyset_cache for secp256k1 sets: the registered set of these n 33-byte
 // keys (built on first use, k_secp_qcomb_build), or NULL when the cache is
 // off or registration failed (the caller then verifies by key bytes).

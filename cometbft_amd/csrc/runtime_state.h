@@ -718,11 +718,9 @@ int enqueue_verify_secp_templated(cmtv_ctx* ctx, CmtvDev& D, size_t n, const uin
 int verify_host_device(cmtv_ctx* ctx, size_t n, const uint8_t* pk, const uint8_t* sig, const uint8_t* msg,
                        const uint32_t* msg_off, uint32_t mode, uint8_t* out_valid, uint64_t* out_bitmap,
                        const cmtv_keyset* ks = nullptr, const uint32_t* key_idx = nullptr);
-int verify_secp_host_locked(cmtv_ctx* ctx, size_t n, const uint8_t* pk, const uint8_t* sig, const uint8_t* msg,
-                            const uint32_t* msg_off, uint8_t* out_valid, uint64_t* out_bitmap);
-int verify_secp_keyed_host_locked(cmtv_ctx* ctx, const cmtv_secp_keyset* ks, size_t n, const uint32_t* key_idx,
-                                  const uint8_t* sig, const uint8_t* msg, const uint32_t* msg_off, uint8_t* out_valid,
-                                  uint64_t* out_bitmap);
+// (keys: n x 33 key bytes, or with ks n u32 indices of its registered keys)
+int verify_secp_host_locked(cmtv_ctx* ctx, const cmtv_secp_keyset* ks, size_t n, const void* keys, const uint8_t* sig,
+                            const uint8_t* msg, const uint32_t* msg_off, uint8_t* out_valid, uint64_t* out_bitmap);
 
 // gather.cpp
 int gather_bitmaps(cmtv_ctx* ctx, const size_t* dev, size_t G, size_t W, uint64_t* const* bufs);

@@ -80,6 +80,7 @@ struct cmtv_ctx {
   uint64_t spec_calls = 0, spec_ok = 0;  // speculative launches, and those whose checks held
   uint32_t spec_min = 2048;               // CMTV_SPEC_MIN / CMTV_SPEC at fake_open
   uint64_t masked_chunks = 0;
+  uint64_t offset_free = 0;  // verify_templated_locked calls without message offsets
 };
 
 namespace {
@@ -180,6 +181,7 @@ int verify_templated_locked(cmtv_ctx* ctx, size_t n, const uint8_t* pk, const ui
                             uint8_t* out_valid, const cmtv_keyset* ks, const uint32_t* key_idx, uint32_t msg_bound,
                             const std::function<bool()>* between, bool* between_ok) {
   ctx->signatures += n;
+  ctx->offset_free += msg_off ? 0 : 1;
   if (between) {  // "after the launch" (the fake verifies below)
     *between_ok = (*between)();
     ctx->spec_calls++;
@@ -526,6 +528,7 @@ extern "C" void fake_counts(cmtv_ctx* c, uint64_t* out) {
   out[5] = c->direct_chunks;
   out[6] = c->spec_calls;
   out[7] = c->spec_ok;
+  out[8] = c->offset_free;
 }
 
 extern "C" void fake_close(cmtv_ctx* c) {

@@ -1,7 +1,7 @@
 // fake_typed_runtime.cpp -- test double of the runtime functions only the
 // typed commit layer calls (runtime_internal.h verify_secp_templated_locked,
-// secp_keyset_for_locked), beside the unchanged fake_runtime.cpp, for
-// tests/host/typedcheck.cpp. The "device" rebuilds each message from its
+// secp_keyset_for_locked), beside fake_runtime.cpp, for
+// tests/host/typedcheck.cpp and tests/host/typedcommitscheck.cpp. The "device" rebuilds each message from its
 // template with signbytes.h sb_write, as the templated kernels do, and
 // verifies with the host-compiled secp256k1.h (secp_verify_one over the fixed
 // table built by secp_gtab_row). Registered keys are looked up in the set's
@@ -57,45 +57,42 @@ struct VecOut {
 };
 
 std::vector<std::unique_ptr<cmtv_secp_keyset>> g_sets;  // kept until exit, as the fake keeps its key sets until close
-uint64_t g_calls = 0, g_keyed_calls = 0, g_sigs = 0;
+// [0..3): calls, calls by registered keys, signatures; [3..7): of the bulk
+// calls (SecpTemplated::bulk), the same three and the templates shipped
+uint64_t g_counts[7] = {};
 
 }  // namespace
 
-extern "C" void fake_typed_counts(uint64_t* out) {
-  out[0] = g_calls;
-  out[1] = g_keyed_calls;
-  out[2] = g_sigs;
-}
+extern "C" void fake_typed_counts(uint64_t* out) { std::memcpy(out, g_counts, sizeof g_counts); }
 
 namespace cmtv {
 
-int verify_secp_templated_locked(cmtv_ctx*, size_t n, const uint8_t* pk33, const cmtv_secp_keyset* ks,
-                                 const uint32_t* key_idx, const uint8_t* sig, const void* tmpls, size_t n_tmpls,
-                                 const uint8_t* blob, size_t, const uint32_t* tidx, const uint8_t* commit_flag,
-                                 const int64_t* sec, const int32_t* nanos, uint8_t* out_valid) {
+int verify_secp_templated_locked(cmtv_ctx*, const SecpTemplated& r, uint8_t* out_valid) {
   static const HostGTab gt;
-  g_calls++;
-  g_keyed_calls += ks ? 1 : 0;
-  g_sigs += n;
-  if (ks ? !key_idx : !pk33) return CMTV_EINVAL;
-  const auto* tp = static_cast<const SbTemplate*>(tmpls);
-  for (size_t i = 0; i < n; i++) {
-    const uint32_t ti = tidx ? tidx[i] : 0u;
-    if (ti >= n_tmpls) return CMTV_EINVAL;
-    const uint32_t len = sb_msg_len(tp[ti], commit_flag[i] != 0, sec[i], nanos[i]);
+  for (int c = 0; c <= (r.bulk ? 3 : 0); c += 3) {
+    g_counts[c]++;
+    g_counts[c + 1] += r.ks ? 1 : 0;
+    g_counts[c + 2] += r.n;
+  }
+  g_counts[6] += r.bulk ? r.n_tmpls : 0;
+  if (r.ks ? !r.key_idx : !r.pk33) return CMTV_EINVAL;
+  const auto* tp = static_cast<const SbTemplate*>(r.tmpls);
+  for (size_t i = 0; i < r.n; i++) {
+    const uint32_t ti = r.tidx ? r.tidx[i] : 0u;
+    if (ti >= r.n_tmpls) return CMTV_EINVAL;
+    const bool for_block = r.commit_flag[i] != 0;
+    const uint32_t len = sb_msg_len(tp[ti], for_block, r.sec[i], r.nanos[i]);
     // word-aligned, with the slack the hash's aligned loads may touch
     std::vector<uint32_t> buf(len / 4 + 2, 0);
     VecOut out{reinterpret_cast<uint8_t*>(buf.data())};
-    if (sb_write(out, tp[ti], blob, commit_flag[i] != 0, sec[i], nanos[i]) != len) return CMTV_EINVAL;
-    const uint8_t* pk;
-    if (ks) {
-      if (key_idx[i] >= ks->n) return CMTV_EINVAL;
-      pk = ks->pk.data() + 33 * (size_t)key_idx[i];
-    } else {
-      pk = pk33 + 33 * i;
+    if (sb_write(out, tp[ti], r.blob, for_block, r.sec[i], r.nanos[i]) != len) return CMTV_EINVAL;
+    const uint8_t* pk = r.pk33 + 33 * i;
+    if (r.ks) {
+      if (r.key_idx[i] >= r.ks->n) return CMTV_EINVAL;
+      pk = r.ks->pk.data() + 33 * (size_t)r.key_idx[i];
     }
     HostQTab qt;
-    out_valid[i] = secp_verify_one(pk, sig + 64 * i, out.p, len, qt, gt) ? 1 : 0;
+    out_valid[i] = secp_verify_one(pk, r.sig + 64 * i, out.p, len, qt, gt) ? 1 : 0;
   }
   return CMTV_OK;
 }

@@ -104,7 +104,7 @@ int main(int argc, char** argv) {
     if (it) best = ms < best ? ms : best;
     if (it == 0) fake_phases(ctx, pt0);  // the phases below leave out the warm-up call (first touch)
   }
-  uint64_t cnt[6];
+  uint64_t cnt[9];
   fake_counts(ctx, cnt);
   std::printf("%zu heights x %u, kind %u, %u threads, %zu devices, %s, %s (%llu direct chunks): %.4f ms per call (%.1f ns per signature of wall)\n", H, nv, kind,
               T, devs, pipe ? "pipeline" : "one batch", pinned ? "pinned arena" : "heap", (unsigned long long)cnt[5], best, best * 1e6 / (double)(H * nv));

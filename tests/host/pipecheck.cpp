@@ -431,7 +431,7 @@ int race(const std::vector<CommitData>& chain, const std::vector<const VSet*>& v
   pipe.join();
   single.join();
   other.join();
-  uint64_t cnt[8];
+  uint64_t cnt[9];
   fake_counts(ctx, cnt);
   fake_close(ctx);
   if (!cnt[5]) {
@@ -481,7 +481,7 @@ int check_template_lens() {
 // in place between calls (the guess must be refuted by the byte compare).
 int check_single(const std::vector<CommitData>& chain, const std::vector<const VSet*>& vals_of) {
   int bad = 0;
-  uint64_t spec = 0, spec_ok = 0, cnt[8];
+  uint64_t spec = 0, spec_ok = 0, cnt[9];
   for (uint32_t kind = 0; kind < 3; kind++) {
     cmtv_ctx* ctx = fake_open(1, 2, 1, 1u << 20, 3, true, 4, -1);
     for (int pass = 0; pass < 2; pass++)
@@ -625,7 +625,7 @@ int main(int argc, char** argv) {
         fake_set_keyset_fail(ctx, c.keyset_fail);
         if (c.tight_spans) fake_set_span(ctx, 1, 0);
         const Run r = run(ctx, kind, mode, chain, vals_of, c.lay);
-        uint64_t cnt[8];
+        uint64_t cnt[9];
         fake_counts(ctx, cnt);
         fake_close(ctx);
         expect_same(c.name, base, r);

@@ -1,8 +1,10 @@
 // typedcheck.cpp -- the typed commit layer (cometbft_amd/csrc/commit_typed.cpp,
-// with commit.cpp) on the CPU, linked against the unchanged fake_runtime.cpp
-// and fake_typed_runtime.cpp, under AddressSanitizer + UBSan: the partition
+// with commit.cpp) on the CPU, linked against fake_runtime.cpp and
+// fake_typed_runtime.cpp, under AddressSanitizer + UBSan: the partition
 // of a plan by key type, the three batches' arrays and the scatter of their
-// verdicts back into plan order.
+// verdicts back into plan order. A single commit never takes the routes of
+// the many-heights call: no secp256k1 batch is a bulk one, and the Ed25519
+// share of a mixed set arrives as one batch without message offsets.
 //
 //   typedcheck FILE
 // FILE holds cases written by tests/test_typed_commit_host.py (little-endian):
@@ -21,51 +23,20 @@
 #include <vector>
 
 #include "../../include/cmtverify.h"
+#include "case_reader.h"
 
 extern "C" {
 cmtv_ctx* fake_open(size_t n_devs, unsigned threads, size_t pipe_min, size_t chunk, int slots, bool pipe_on,
                     size_t keyset_cap, long fail_dev);
 void fake_close(cmtv_ctx* c);
+void fake_counts(cmtv_ctx* c, uint64_t* out);
 void fake_typed_counts(uint64_t* out);
 }
-
-namespace {
-
-struct Reader {
-  std::vector<uint8_t> d;
-  size_t at = 0;
-  template <class T>
-  T get() {
-    T v;
-    if (at + sizeof(T) > d.size()) {
-      std::fprintf(stderr, "typedcheck: truncated input\n");
-      std::exit(2);
-    }
-    std::memcpy(&v, &d[at], sizeof(T));
-    at += sizeof(T);
-    return v;
-  }
-  std::vector<uint8_t> bytes(size_t n) {
-    if (at + n > d.size()) {
-      std::fprintf(stderr, "typedcheck: truncated input\n");
-      std::exit(2);
-    }
-    std::vector<uint8_t> v(d.begin() + (long)at, d.begin() + (long)(at + n));
-    at += n;
-    return v;
-  }
-};
-
-}  // namespace
 
 int main(int argc, char** argv) {
   if (argc < 2) return 2;
   Reader r;
-  FILE* f = std::fopen(argv[1], "rb");
-  if (!f) return 2;
-  uint8_t buf[65536];
-  for (size_t n; (n = std::fread(buf, 1, sizeof buf, f)) > 0;) r.d.insert(r.d.end(), buf, buf + n);
-  std::fclose(f);
+  if (!r.load(argv[1])) return 2;
   const uint32_t n_cases = r.get<uint32_t>();
   int bad = 0;
   for (uint32_t c = 0; c < n_cases; c++) {
@@ -76,10 +47,12 @@ int main(int argc, char** argv) {
     const uint32_t nv = r.get<uint32_t>();
     // exact-size arrays, so that AddressSanitizer sees any read past them
     std::vector<uint8_t> types(nv), keys, addrs;
+    bool any_ed = false, any_other = false;
     std::vector<uint32_t> pk_off(nv + 1, 0);
     std::vector<int64_t> power(nv), prio(nv, 0);
     for (uint32_t i = 0; i < nv; i++) {
       types[i] = r.get<uint8_t>();
+      (types[i] == CMTV_KEY_ED25519 ? any_ed : any_other) = true;
       const auto k = r.bytes(r.get<uint32_t>());
       keys.insert(keys.end(), k.begin(), k.end());
       pk_off[i + 1] = (uint32_t)keys.size();
@@ -125,7 +98,7 @@ int main(int argc, char** argv) {
     const int32_t want_keyed = r.get<int32_t>();
 
     cmtv_ctx* ctx = fake_open(1, 1, (size_t)1 << 40, 1u << 20, 3, false, cap, -1);
-    uint64_t c0[3], c1[3];
+    uint64_t c0[7], c1[7], cnt[9];
     fake_typed_counts(c0);
     cmtv_commit_result res{};
     char msg[2048];
@@ -133,12 +106,16 @@ int main(int argc, char** argv) {
                                             chain.size(), &vs, types.data(), &cm.block_id, height, &cm, num, den, &res,
                                             msg, sizeof msg);
     fake_typed_counts(c1);
+    fake_counts(ctx, cnt);
     fake_close(ctx);
     const int keyed = c1[0] == c0[0] ? -1 : (c1[1] > c0[1] ? 1 : 0);
-    const bool ok = rc == want_rc && res.code == want_code && (want_idx == -2 || res.sig_index == want_idx) &&
+    // no bulk call; a mixed set's Ed25519 share is the context's one offset-free templated batch
+    const bool routes = c1[3] == c0[3] && cnt[8] == (any_ed && any_other ? 1u : 0u);
+    const bool ok = routes && rc == want_rc && res.code == want_code && (want_idx == -2 || res.sig_index == want_idx) &&
                     want_msg == msg && res.n_verified == want_nv && keyed == want_keyed;
-    std::printf("case %u: rc %d code %d index %d verified %u keyed %d %s\n", c, rc, res.code, res.sig_index,
-                res.n_verified, keyed, ok ? "ok" : "MISMATCH");
+    std::printf("case %u: rc %d code %d index %d verified %u keyed %d bulk %llu offset-free %llu %s\n", c, rc, res.code,
+                res.sig_index, res.n_verified, keyed, (unsigned long long)(c1[3] - c0[3]), (unsigned long long)cnt[8],
+                ok ? "ok" : "MISMATCH");
     if (!ok) {
       std::printf("  want rc %d code %d index %d verified %u keyed %d\n  got  \"%s\"\n  want \"%s\"\n", want_rc, want_code,
                   want_idx, want_nv, want_keyed, msg, want_msg.c_str());

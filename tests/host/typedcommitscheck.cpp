@@ -1,10 +1,10 @@
 // typedcommitscheck.cpp -- the cross-height typed commit layer
-// (cometbft_amd/csrc/commits_typed.cpp, with commit.cpp, commit_typed.cpp and
-// pipeline.cpp) on the CPU, linked against the unchanged fake_runtime.cpp and
-// fake_typed_runtime.cpp and the double of its own runtime function
-// (fake_typed_bulk_runtime.cpp), under AddressSanitizer + UBSan: the
-// grouping of commits by registered set, the per-group templates, the
-// partition by key type across commits, the scatter and the per-commit replay.
+// (cmtv_verify_commits_typed in cometbft_amd/csrc/commit_typed.cpp, with
+// commit.cpp and pipeline.cpp) on the CPU, linked against fake_runtime.cpp
+// and fake_typed_runtime.cpp, under AddressSanitizer + UBSan: the grouping of
+// commits by registered set, the per-group templates, the partition by key
+// type across commits, the scatter and the per-commit replay; every
+// secp256k1 batch a bulk one, no Ed25519 batch without message offsets.
 //
 //   typedcommitscheck FILE
 // FILE holds cases written by tests/test_typed_commits_host.py (little-endian):
@@ -31,40 +31,17 @@
 #include <vector>
 
 #include "../../include/cmtverify.h"
+#include "case_reader.h"
 
 extern "C" {
 cmtv_ctx* fake_open(size_t n_devs, unsigned threads, size_t pipe_min, size_t chunk, int slots, bool pipe_on,
                     size_t keyset_cap, long fail_dev);
 void fake_close(cmtv_ctx* c);
-void fake_typed_bulk_counts(uint64_t* out);
+void fake_counts(cmtv_ctx* c, uint64_t* out);
+void fake_typed_counts(uint64_t* out);  // [3..7): bulk calls, those by registered keys, signatures, templates shipped
 }
 
 namespace {
-
-struct Reader {
-  std::vector<uint8_t> d;
-  size_t at = 0;
-  void need(size_t n) {
-    if (at + n > d.size()) {
-      std::fprintf(stderr, "typedcommitscheck: truncated input\n");
-      std::exit(2);
-    }
-  }
-  template <class T>
-  T get() {
-    T v;
-    need(sizeof(T));
-    std::memcpy(&v, &d[at], sizeof(T));
-    at += sizeof(T);
-    return v;
-  }
-  std::vector<uint8_t> bytes(size_t n) {
-    need(n);
-    std::vector<uint8_t> v(d.begin() + (long)at, d.begin() + (long)(at + n));
-    at += n;
-    return v;
-  }
-};
 
 // One commit's arguments in exact-size arrays, so that AddressSanitizer sees
 // any read past them
@@ -145,11 +122,7 @@ std::unique_ptr<Height> read_height(Reader& r) {
 int main(int argc, char** argv) {
   if (argc < 2) return 2;
   Reader r;
-  FILE* f = std::fopen(argv[1], "rb");
-  if (!f) return 2;
-  uint8_t buf[65536];
-  for (size_t n; (n = std::fread(buf, 1, sizeof buf, f)) > 0;) r.d.insert(r.d.end(), buf, buf + n);
-  std::fclose(f);
+  if (!r.load(argv[1])) return 2;
   const uint32_t n_cases = r.get<uint32_t>();
   constexpr size_t kCap = 2048;
   int bad = 0;
@@ -179,18 +152,21 @@ int main(int argc, char** argv) {
     std::vector<char> msgs(n * kCap, 'x');
 
     cmtv_ctx* ctx = fake_open(1, 1, (size_t)1 << 40, 1u << 20, 3, false, cap, -1);
-    uint64_t c0[4], c1[4];
-    fake_typed_bulk_counts(c0);
+    uint64_t c0[7], c1[7], cnt[9];
+    fake_typed_counts(c0);
     const int rc = cmtv_verify_commits_typed(ctx, kind, CMTV_MODE_GO_STDLIB, cid, chain.size(), n, vals.data(),
                                              types_mode == 1 ? nullptr : types.data(), bids.data(), heights.data(),
                                              commits.data(), num, den, res.data(), rcs.data(), msgs.data(), kCap);
-    fake_typed_bulk_counts(c1);
+    fake_typed_counts(c1);
+    fake_counts(ctx, cnt);
     fake_close(ctx);
     bool ok = rc == CMTV_OK;
-    const int bulk = (int)(c1[0] - c0[0]), keyed = (int)(c1[1] - c0[1]);
+    const int bulk = (int)(c1[3] - c0[3]), keyed = (int)(c1[4] - c0[4]);
     ok = ok && (want_bulk < 0 || bulk == want_bulk) && (want_keyed < 0 || keyed == want_keyed);
+    // every secp256k1 batch is a bulk one, and no templated batch comes without offsets
+    ok = ok && c1[0] - c0[0] == c1[3] - c0[3] && cnt[8] == 0;
     // a group ships its own commits' templates only
-    ok = ok && c1[3] - c0[3] <= (uint64_t)n;
+    ok = ok && c1[6] - c0[6] <= (uint64_t)n;
     std::printf("case %u: rc %d, %u commits, %d bulk calls (%d keyed)%s\n", c, rc, n, bulk, keyed, ok ? "" : " MISMATCH");
     for (uint32_t i = 0; i < n && rc == CMTV_OK; i++) {
       const Height& h = *hs[i];

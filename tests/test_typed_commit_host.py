@@ -1,7 +1,10 @@
 """CPU check of the typed commit layer (tests/host/typedcheck.cpp):
-cometbft_amd/csrc/commit_typed.cpp and commit.cpp compiled unchanged, with
-AddressSanitizer + UBSan, against the unchanged tests/host/fake_runtime.cpp
-and tests/host/fake_typed_runtime.cpp, as a stand-alone program run directly.
+cmtv_verify_commit_typed in cometbft_amd/csrc/commit_typed.cpp, with
+commit.cpp and pipeline.cpp, compiled unchanged with AddressSanitizer + UBSan
+against tests/host/fake_runtime.cpp and tests/host/fake_typed_runtime.cpp, as
+a stand-alone program run directly. The program also holds a single commit to
+its own routes: no bulk secp256k1 batch, and a mixed set's Ed25519 share as
+one batch without message offsets.
 
 The doubles verify Ed25519 with the C oracle, secp256k1 with the
 host-compiled secp256k1.h over messages rebuilt from the templates, and the
@@ -39,7 +42,8 @@ CHAIN, HEIGHT = "typed-host", 9
 
 
 def _build():
-    deps = SRCS + [os.path.join(ROOT, "oracle", "cmtv_oracle.c"), os.path.join(ROOT, "include", "cmtverify.h")] + \
+    deps = SRCS + [os.path.join(HOST, "case_reader.h"), os.path.join(ROOT, "oracle", "cmtv_oracle.c"),
+                   os.path.join(ROOT, "include", "cmtverify.h")] + \
         [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")]
     if os.path.exists(BIN) and os.path.getmtime(BIN) >= max(os.path.getmtime(d) for d in deps):
         return BIN

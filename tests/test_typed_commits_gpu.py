@@ -347,6 +347,13 @@ def test_batched_kernel(cache_ctx, min_waves, n_heights, n_vals, kb):
             assert got == many(cache_ctx, kind, hs)
             c1 = cache_ctx.stats()
             assert c1["secp_batch_launches"] == c0["secp_batch_launches"] and c1["keyed_launches"] > c0["keyed_launches"]
+        # cmtv_verify_commit_typed never batches, whatever the knob says: the
+        # first height alone is one one-signature-per-lane launch
+        s0 = ctx.stats()
+        same(loop(ctx, "full", hs[:1]), want[:1])
+        s1 = ctx.stats()
+        assert s1["secp_batch_launches"] == s0["secp_batch_launches"]
+        assert s1["keyed_launches"] - s0["keyed_launches"] == 1
     finally:
         ctx.close()
 

@@ -1,10 +1,10 @@
 """CPU check of the cross-height typed commit layer
-(tests/host/typedcommitscheck.cpp): cometbft_amd/csrc/commits_typed.cpp with
-commit.cpp, commit_typed.cpp and pipeline.cpp compiled unchanged, with
-AddressSanitizer + UBSan, against the unchanged tests/host/fake_runtime.cpp
-and tests/host/fake_typed_runtime.cpp and the double of the one runtime
-function the new file adds (tests/host/fake_typed_bulk_runtime.cpp), as a
-stand-alone program run directly.
+(tests/host/typedcommitscheck.cpp): cmtv_verify_commits_typed in
+cometbft_amd/csrc/commit_typed.cpp, with commit.cpp and pipeline.cpp, compiled
+unchanged with AddressSanitizer + UBSan against tests/host/fake_runtime.cpp
+and tests/host/fake_typed_runtime.cpp (which counts the bulk secp256k1
+batches, their signatures and the templates they ship), as a stand-alone
+program run directly.
 
 Expected outcomes are tests/typed_commit_ref.py's loops, height by height
 (with the sr25519 verifier swapped for the fake runtime's stand-in, as
@@ -30,9 +30,8 @@ CSRC = os.path.join(ROOT, "cometbft_amd", "csrc")
 HOST = os.path.join(ROOT, "tests", "host")
 BIN = os.path.join(ROOT, "build", "typedcommitscheck")
 SRCS = [os.path.join(HOST, "typedcommitscheck.cpp"), os.path.join(HOST, "fake_runtime.cpp"),
-        os.path.join(HOST, "fake_typed_runtime.cpp"), os.path.join(HOST, "fake_typed_bulk_runtime.cpp"),
-        os.path.join(CSRC, "commit.cpp"), os.path.join(CSRC, "commit_typed.cpp"),
-        os.path.join(CSRC, "commits_typed.cpp"), os.path.join(CSRC, "pipeline.cpp")]
+        os.path.join(HOST, "fake_typed_runtime.cpp"), os.path.join(CSRC, "commit.cpp"),
+        os.path.join(CSRC, "commit_typed.cpp"), os.path.join(CSRC, "pipeline.cpp")]
 FLAGS = ["-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-omit-frame-pointer",
          "-D__HIP_PLATFORM_AMD__", "-I/opt/rocm/include"]
 KINDS = {"full": 0, "light": 1, "trusting": 2}
@@ -43,7 +42,8 @@ CHAIN = "typed-heights"
 
 
 def _build():
-    deps = SRCS + [os.path.join(ROOT, "oracle", "cmtv_oracle.c"), os.path.join(ROOT, "include", "cmtverify.h")] + \
+    deps = SRCS + [os.path.join(HOST, "case_reader.h"), os.path.join(ROOT, "oracle", "cmtv_oracle.c"),
+                   os.path.join(ROOT, "include", "cmtverify.h")] + \
         [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")]
     if os.path.exists(BIN) and os.path.getmtime(BIN) >= max(os.path.getmtime(d) for d in deps):
         return BIN
