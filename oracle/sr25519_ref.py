@@ -315,6 +315,45 @@ def ristretto_decode(b: bytes):
     return (x, y, 1, t)
 
 
+DECODE_RULES = ("canonical", "nonneg_s", "was_square", "nonneg_t", "nonzero_y")
+
+
+def ristretto_decode_lenient(b: bytes, skip=()):
+    """DECODE with the rules named in `skip` (of DECODE_RULES) not applied: what
+    a decoder that lacks them hands on. With "canonical" skipped the field
+    element is read as a field decoder reads it (bit 255 ignored, the value
+    taken mod p); with "was_square" skipped the coordinates are the formulas'
+    field elements, on the curve or not. skip = () is ristretto_decode. Test
+    infrastructure for the discriminating vectors of
+    tests/golden/make_sr25519_corpus.py: a vector pins a rule only if the strict
+    decoder's verdict and this one's differ on it."""
+    assert len(b) == 32 and set(skip) <= set(DECODE_RULES), skip
+    raw = int.from_bytes(b, "little")
+    if "canonical" not in skip and raw >= P:
+        return None
+    s = (raw & (2**255 - 1)) % P
+    if "nonneg_s" not in skip and s & 1:
+        return None
+    ss = s * s % P
+    u1 = (1 - ss) % P
+    u2 = (1 + ss) % P
+    u2_sqr = u2 * u2 % P
+    v = (-(D * u1 % P * u1) - u2_sqr) % P
+    was_square, invsqrt = sqrt_ratio_m1(1, v * u2_sqr % P)
+    den_x = invsqrt * u2 % P
+    den_y = invsqrt * den_x % P * v % P
+    x = _abs(2 * s * den_x)
+    y = u1 * den_y % P
+    t = x * y % P
+    if "was_square" not in skip and not was_square:
+        return None
+    if "nonneg_t" not in skip and _is_neg(t):
+        return None
+    if "nonzero_y" not in skip and y == 0:
+        return None
+    return (x, y, 1, t)
+
+
 def ristretto_encode(p) -> bytes:
     """RFC 9496 4.3.2 ENCODE."""
     x0, y0, z0, t0 = p
@@ -382,6 +421,23 @@ def verify(pub: bytes, msg: bytes, sig: bytes) -> bool:
     return ristretto_equal(Rp, R)
 
 
+def verify_lenient(pub: bytes, msg: bytes, sig: bytes, skip_pk=(), skip_r=()) -> bool:
+    """verify() with ristretto_decode_lenient for the key (skip_pk) and for R
+    (skip_r): the verdict of a verifier without those decode rules. The
+    transcript runs over the bytes as given, as in verify()."""
+    if len(sig) != SIGNATURE_SIZE:
+        return False
+    p = (bytes(pub) + b"\x00" * 32)[:32]
+    A = ristretto_decode_lenient(p, skip_pk)
+    R = ristretto_decode_lenient(sig[:32], skip_r)
+    s = int.from_bytes(sig[32:63] + bytes([sig[63] & 0x7F]), "little")
+    if A is None or R is None or sig[63] & 0x80 == 0 or s >= L:
+        return False
+    k = challenge(signing_context(b"", msg), p, sig[:32])
+    Rp = point_add(scalar_mult(s, B), point_neg(scalar_mult(k, A)))
+    return ristretto_equal(Rp, R)
+
+
 def expand_mini(mini: bytes):
     """MiniSecretKey.ExpandEd25519: h = SHA-512(mini); key = clamp(h[:32]) / 8
     (divideScalarByCofactor); nonce = h[32:]."""
@@ -411,3 +467,14 @@ def sign(mini: bytes, msg: bytes, nonce_seed: bytes = b"") -> bytes:
     sb = bytearray(s.to_bytes(32, "little"))
     sb[31] |= 0x80
     return Rb + bytes(sb)
+
+
+def sign_encoded(a: int, r: int, msg: bytes, pk_enc: bytes, r_enc: bytes) -> bytes:
+    """s = r + k a with the challenge taken over pk_enc and r_enc as given: the
+    signature of a signer who presents chosen encodings of its key [a]B and of
+    R = [r]B (test data for decoders: with the canonical encodings this is
+    sign()'s equation)."""
+    k = challenge(signing_context(b"", msg), pk_enc, r_enc)
+    sb = bytearray(((r + k * a) % L).to_bytes(32, "little"))
+    sb[31] |= 0x80
+    return bytes(r_enc) + bytes(sb)

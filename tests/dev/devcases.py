@@ -6,7 +6,10 @@ arbitrary-precision arithmetic (points: oracle/ed25519_ref.py). The lane
 checks (LANE_CHECKS) run both on the GPU (tests/test_device_primitives_gpu.py)
 and through the DEVCHECK_HOST build (tests/test_device_primitives_host.py),
 which is what shows the generators and references right before a GPU is
-involved; the row and quad checks need the device's lane exchanges.
+involved; the row and quad checks need the device's lane exchanges. The
+lane checks end with the verdicts' rejection rules (ristretto_decode,
+secp_parse_pubkey, secp_sig_scalars, secp_x_is_r and the point formulas)
+against oracle/sr25519_ref.py and tests/secp256k1_ref.py.
 
 Where the operand bounds come from:
   MUL_BOUND, SQ_ODD_BOUND   fe25519.h (19 g_i / 38 f_i must fit 32 bits)
@@ -14,6 +17,7 @@ Where the operand bounds come from:
   0x10000 + 128             row.h "carried" limbs; the bound rowcheck asserts
 """
 import hashlib
+import json
 import os
 import struct
 import subprocess
@@ -22,6 +26,7 @@ import numpy as np
 
 from oracle import ed25519_ref as E
 from oracle import sr25519_ref
+from tests import secp256k1_ref
 
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 P = 2**255 - 19
@@ -395,6 +400,296 @@ def check_keccak(run):
         assert out[j].tobytes() == bytes(st), j
 
 
+# ---- the verdicts' rejection rules (sr25519.h, secp256k1.h) ---------------------------------
+# One record per lane, whole waves of different inputs; verdicts and values
+# compared exactly with oracle/sr25519_ref.py and tests/secp256k1_ref.py.
+
+def _sr_corpus_encodings():
+    """every key and R of the sr25519 corpus's encoding categories: all of the
+    generator's RFC_BAD, the decode_pk / decode_r alternative encodings, the
+    non-canonical / negative / random ones of pk_encoding / r_encoding"""
+    with open(os.path.join(ROOT, "tests", "golden", "sr25519_corpus.json")) as f:
+        vecs = json.load(f)["vectors"]
+    cats = {"rfc_bad", "decode_pk", "decode_r", "pk_encoding", "r_encoding"}
+    encs = []
+    for v in vecs:
+        if v["cat"] in cats:
+            for e in (bytes.fromhex(v["pk"]), bytes.fromhex(v["sig"])[:32]):
+                if e not in encs:
+                    encs.append(e)
+    return encs
+
+
+def check_ristretto_decode(run):
+    """ristretto_decode's verdict on every input, its point where the strict
+    oracle accepts. The case set holds, for each of the five rules, encodings
+    that break that rule alone (asserted): this is what pins was_square, which
+    no signature can reach (tests/golden/make_sr25519_corpus.py)."""
+    S = sr25519_ref
+    rng = np.random.default_rng(60)
+    encs = _sr_corpus_encodings()
+    encs += [v.to_bytes(32, "little") for v in (0, P - 1, P, P + 1, 2**255 - 1, 2**255, 2**256 - 1, 1, 2, P - 2)]
+    mult = [S.ristretto_encode(S.scalar_mult(k, S.B)) for k in range(1, 17)]
+    encs += mult + [(int.from_bytes(e, "little") | 1 << 255).to_bytes(32, "little") for e in mult[:4]]
+    while len(encs) % 64 or len(encs) < 320:
+        encs.append((int.from_bytes(rng.bytes(32), "little") % P & ~1).to_bytes(32, "little"))  # about 1 in 8 decodes
+    out = run("ristretto_decode", [np.frombuffer(e, np.uint32) for e in encs]).tolist()
+    alone = set()
+    for j, e in enumerate(encs):
+        pt = S.ristretto_decode(e)
+        assert out[j][0] == int(pt is not None), (j, e.hex())
+        if pt is not None:
+            got = tuple(unwords(out[j][1 + 8 * c: 9 + 8 * c]) for c in range(3))
+            assert got == (pt[0], pt[1], pt[3]), (j, e.hex())
+        else:
+            broken = [r for r in S.DECODE_RULES
+                      if S.ristretto_decode_lenient(e, tuple(set(S.DECODE_RULES) - {r})) is None]
+            if len(broken) == 1:
+                alone.add(broken[0])
+    assert alone == set(S.DECODE_RULES), alone
+    assert sum(o[0] for o in out) >= 32
+
+
+def check_sqrt_ratio_m1(run):
+    """fe_sqrt_ratio_m1 against RFC 9496's SQRT_RATIO_M1: u / v square, i u / v
+    square, u = 0, v = 0, both; u, v carried (canonical-width limbs)"""
+    rng = np.random.default_rng(61)
+
+    def rnd():
+        return int.from_bytes(rng.bytes(32), "little") % P or 1
+
+    cases = [(0, 0), (0, 1), (1, 0), (1, 1), (P - 1, 1), (1, P - 1), (SQRT_M1, 1), (P - SQRT_M1, 1), (4, 1), (1, 4),
+             (2**255 - 20, 2**255 - 20), (2, 1), (1, 2)]
+    while len(cases) % 64 or len(cases) < 256:
+        r0, v = rnd(), rnd()
+        k = len(cases) % 4
+        cases.append([(r0 * r0 * v % P, v), (SQRT_M1 * r0 * r0 * v % P, v), (0, v), (r0, 0)][k])
+    out = run("sqrt_ratio_m1", [fe_limbs(u) + fe_limbs(v) for u, v in cases]).tolist()
+    seen = set()
+    for j, (u, v) in enumerate(cases):
+        sq, r = sr25519_ref.sqrt_ratio_m1(u, v)
+        assert out[j][0] == int(sq) and unwords(out[j][1:]) == r, (j, u, v)
+        assert r & 1 == 0 and (v * r * r - (u if sq else SQRT_M1 * u)) % P == 0 or v == 0, j  # the definition
+        seen.add((bool(sq), u == 0, v == 0))
+    assert seen >= {(True, False, False), (False, False, False), (True, True, False), (False, False, True),
+                    (True, True, True)}  # (was_square, u = 0, v = 0)
+
+
+K = secp256k1_ref
+FP_P = K.P
+FP_M26, FP_M22 = 2**26 - 1, 2**22 - 1
+FP_P_LIMBS = [0x3FFFC2F, 0x3FFFFBF] + [FP_M26] * 7 + [FP_M22]
+
+
+def fp_limbs(v):
+    assert 0 <= v < 2**256
+    return [(v >> (26 * i)) & FP_M26 for i in range(9)] + [v >> 234]
+
+
+def fp_val(limbs):
+    return sum(int(x) << (26 * i) for i, x in enumerate(limbs))
+
+
+def fp_mag(v, m):
+    """v mod p at magnitude m (fp256k1.h): canonical limbs plus (2 m - 1) p
+    limb-wise, every limb between (2 m - 1) / (2 m) of its bound and the bound"""
+    out = [a + (2 * m - 1) * b for a, b in zip(fp_limbs(v % FP_P), FP_P_LIMBS)]
+    assert fp_within(out, m) and not fp_within(out, m - 1) and fp_val(out) % FP_P == v % FP_P
+    return out
+
+
+def fp_within(limbs, m):
+    return all(int(x) <= 2 * m * FP_M26 for x in limbs[:9]) and int(limbs[9]) <= 2 * m * FP_M22
+
+
+def check_secp_parse_pubkey(run):
+    """secp_parse_pubkey: every prefix, x at and around p (never reduced), x + p
+    for small x on the curve, x off the curve, both parities"""
+    rng = np.random.default_rng(62)
+    on = [x for x in range(1, 40) if K.lift_x(x, 0) is not None][:6]
+    off = [x for x in range(1, 40) if K.lift_x(x, 0) is None][:6]
+    assert on and off
+    keys = []
+    for x in on + off + [FP_P - 1, FP_P, FP_P + 1, 2**256 - 1, 0, K.GX] + [x + FP_P for x in on]:
+        for prefix in (2, 3):
+            keys.append(bytes([prefix]) + x.to_bytes(32, "big"))
+    for prefix in (0, 1, 2, 3, 4, 5, 6, 7, 0xFF, 0x82, 0x12):
+        keys.append(bytes([prefix]) + K.GX.to_bytes(32, "big"))
+    while len(keys) % 64 or len(keys) < 256:
+        k = len(keys) % 8
+        x = int.from_bytes(rng.bytes(32), "big")
+        if k == 7:
+            x |= (2**256 - 2**33)  # x >= p about half of the time
+        keys.append(bytes([(2, 3, 2, 3, 3, 2, int(rng.integers(0, 256)), 2)[k]]) + x.to_bytes(32, "big"))
+    out = run("secp_parse_pubkey", [np.frombuffer(k + b"\0\0\0", np.uint32) for k in keys]).tolist()
+    seen = set()
+    for j, k in enumerate(keys):
+        q = K.parse_pubkey(k)
+        assert out[j][0] == int(q is not None), (j, k.hex())
+        if q is not None:
+            assert (unwords(out[j][1:9]), unwords(out[j][9:17])) == (q[0], q[1]), (j, k.hex())
+            seen.add(q[1] & 1)
+    assert seen == {0, 1} and 32 <= sum(o[0] for o in out) <= len(keys) - 32
+    # x + p for x on the curve is rejected only by x < p
+    assert all(K.parse_pubkey(bytes([2]) + (x + FP_P).to_bytes(32, "big")) is None for x in on)
+
+
+def check_secp_sig_scalars(run):
+    """secp_sig_scalars: r and s reduced mod n; false for r = 0, s = 0 (also as
+    the bytes of n) and s above (n - 1) / 2"""
+    rng = np.random.default_rng(63)
+    n = K.N
+    edge = [0, 1, n - 1, n, n + 1, (n - 1) // 2, (n + 1) // 2, 2**256 - 1]
+    cases = [(r, s) for r in edge for s in edge]
+    while len(cases) % 64 or len(cases) < 256:
+        r, s = (int.from_bytes(rng.bytes(32), "big") for _ in range(2))
+        cases.append((r, s >> int(rng.integers(0, 3))))
+    recs = [np.frombuffer(r.to_bytes(32, "big") + s.to_bytes(32, "big"), np.uint32) for r, s in cases]
+    out = run("secp_sig_scalars", recs).tolist()
+    for j, (r, s) in enumerate(cases):
+        ok = r % n != 0 and s % n != 0 and s % n <= K.HALF_N
+        assert out[j] == [int(ok)] + words(r % n, 8) + words(s % n, 8), (j, hex(r), hex(s))
+    # r = 0 alone: everything else about the signature passes
+    assert sum(1 for r, s in cases if r % n == 0 and 0 < s % n <= K.HALF_N) >= 6
+
+
+def _acc(x, z, mags, y=None):
+    """the accumulator (x z : y z : z) at magnitudes mags = (mx, my, mz)"""
+    y = 1 if y is None else y
+    return fp_mag(x * z, mags[0]) + fp_mag(y * z, mags[1]) + fp_mag(z, mags[2])
+
+
+def check_secp_x_is_r(run):
+    """secp_x_is_r on constructed accumulators (x z : y : z), z random,
+    canonical limbs and magnitude (3, 2, 2): x = r; x = r + n < p; the two ways
+    r + n can leave the field (r + n >= 2^256 with x = r + n - 2^256, and
+    p <= r + n < 2^256 with x = r + n - p: both false, only `wraps` says so);
+    Z = 0 = X (false, only the Z test says so); x = r + 1"""
+    rng = np.random.default_rng(64)
+    n, p = K.N, FP_P
+
+    def below(lo, hi):
+        return lo + int.from_bytes(rng.bytes(40), "big") % (hi - lo)
+
+    cases = []  # (limbs, r, class)
+    for t in range(40):
+        mags = (3, 2, 2) if t & 1 else (1, 1, 1)
+        z = below(1, p)
+        r = [1, p - n - 1, n - 1][t] if t < 3 else below(1, n)
+        if r < n - 1:
+            cases.append((_acc(r, z, mags), r, "x = r"))
+            cases.append((_acc(r + 1, z, mags), r, "x = r + 1"))
+        r = [1, p - n - 1][t] if t < 2 else below(1, p - n)
+        cases.append((_acc(r + n, z, mags), r, "x = r + n"))
+        r = [2**256 - n, n - 1][t] if t < 2 else below(2**256 - n, n)
+        cases.append((_acc(r + n - 2**256, z, mags), r, "wraps 2^256"))
+        r = [p - n, 2**256 - n - 1][t] if t < 2 else below(p - n, 2**256 - n)
+        cases.append((_acc(r + n - p, z, mags), r, "wraps p"))
+        r = below(1, n)
+        cases.append((fp_mag(0, mags[0]) + fp_mag(below(1, p), mags[1]) + fp_mag(0, mags[2]), r, "infinity"))
+        cases.append(([0] * 10 + fp_limbs(1) + [0] * 10, r, "infinity"))
+    while len(cases) % 64:
+        r = below(1, n)
+        cases.append((_acc(below(0, p), below(1, p), (3, 2, 2)), r, "random"))
+    out = run("secp_x_is_r", [l + words(r, 8) for l, r, _ in cases]).tolist()
+    want_by_class = {"x = r": 1, "x = r + n": 1, "x = r + 1": 0, "wraps 2^256": 0, "wraps p": 0, "infinity": 0}
+    for j, (l, r, cls) in enumerate(cases):
+        X, Z = fp_val(l[:10]) % p, fp_val(l[20:]) % p
+        want = int(Z != 0 and X * pow(Z, p - 2, p) % p % n == r)
+        assert want == want_by_class.get(cls, want), (j, cls)
+        assert out[j][0] == want, (j, cls, hex(r))
+        if cls.startswith("wraps"):  # r + n read as 256 bits and as a field element gives X = that Z
+            assert ((r + n) % 2**256 * Z - X) % p == 0, j
+    assert {c for _, _, c in cases} >= set(want_by_class)
+
+
+def _secp_points():
+    """affine points: G, 2G, 3G, [n - 1]G, the x = 1 point, random multiples"""
+    rng = np.random.default_rng(65)
+    pts = [K.to_affine(K.gmul(k)) for k in (1, 2, 3, K.N - 1, K.N - 2)] + [K.lift_x(1, 0)[:2]]
+    pts += [K.to_affine(K.gmul(int.from_bytes(rng.bytes(32), "big") % K.N or 1)) for _ in range(26)]
+    return pts
+
+
+def _proj(pt, z, mags, yneg=False):
+    """(x z : y z : z) at magnitudes mags; None: infinity (0 : z : 0)"""
+    if pt is None:
+        return fp_mag(0, mags[0]) + fp_mag(z, mags[1]) + fp_mag(0, mags[2])
+    x, y = pt
+    return fp_mag(x * z, mags[0]) + fp_mag((-y if yneg else y) * z, mags[1]) + fp_mag(z, mags[2])
+
+
+def _aff_neg(pt):
+    return None if pt is None else (pt[0], -pt[1] % FP_P)
+
+
+def _check_point_out(row, want, mags, what):
+    l = [row[0:10], row[10:20], row[20:30]]
+    assert row[30] == 7 and all(fp_within(a, m) for a, m in zip(l, mags)), (what, "magnitude")
+    X, Y, Z = (fp_val(a) % FP_P for a in l)
+    if want is None:
+        assert X == 0 and Z == 0 and Y != 0, (what, "infinity")
+    else:
+        zi = pow(Z, FP_P - 2, FP_P)
+        assert Z != 0 and (X * zi % FP_P, Y * zi % FP_P) == tuple(want), what
+
+
+def _aff_add(a, b):
+    s = K.jadd(None if a is None else (a[0], a[1], 1), None if b is None else (b[0], b[1], 1))
+    return None if s is None else K.to_affine(s)
+
+
+def check_pt_add(run):
+    """pt_add (complete, RCB algorithm 7) against affine big-integer addition:
+    P + P, P + (-P), infinity on either side and on both, a table entry with Y
+    negated at (3, 3, 2), both operands at (3, 3, 2), canonical limbs; the
+    output within (3, 2, 2)"""
+    rng = np.random.default_rng(66)
+    pts = _secp_points()
+
+    def z():
+        return int.from_bytes(rng.bytes(32), "big") % FP_P or 1
+
+    tight, acc, entry = (1, 1, 1), (3, 2, 2), (3, 3, 2)
+    cases = []  # (p limbs, q limbs, affine sum)
+    for i, a in enumerate(pts):
+        b = pts[(i + 7) % len(pts)]
+        for ma, mb in ((tight, tight), (acc, entry), (entry, entry)):
+            cases.append((_proj(a, z(), ma), _proj(a, z(), mb), _aff_add(a, a)))                      # P + P
+            cases.append((_proj(a, z(), ma), _proj(a, z(), mb, yneg=True), None))                      # P + (-P)
+            cases.append((_proj(a, z(), ma), _proj(b, z(), mb, yneg=True), _aff_add(a, _aff_neg(b))))  # P - Q
+            cases.append((_proj(a, z(), ma), _proj(b, z(), mb), _aff_add(a, b)))
+        cases.append((_proj(None, z(), acc), _proj(a, z(), entry), a))
+        cases.append((_proj(a, z(), acc), _proj(None, z(), entry), a))
+        cases.append((_proj(None, z(), acc), _proj(None, z(), entry), None))
+        cases.append((_proj(None, 1, tight), _proj(a, 1, tight), a))
+    while len(cases) % 64:
+        a, b = pts[len(cases) % len(pts)], pts[(3 * len(cases) + 1) % len(pts)]
+        cases.append((_proj(a, z(), entry), _proj(b, z(), acc), _aff_add(a, b)))
+    out = run("pt_add", [a + b for a, b, _ in cases]).tolist()
+    for j, (_, _, want) in enumerate(cases):
+        _check_point_out(out[j], want, (3, 2, 2), ("pt_add", j))
+    assert sum(1 for c in cases if c[2] is None) >= 64
+
+
+def check_pt_double(run):
+    """pt_double (RCB algorithm 9) against affine doubling: points and
+    infinity, canonical limbs and magnitudes (3, 2, 2) and (3, 3, 2); the
+    output within (2, 2, 1)"""
+    rng = np.random.default_rng(67)
+    cases = []
+    for a in [None, None] + _secp_points():
+        for mags in ((1, 1, 1), (3, 2, 2), (3, 3, 2), (2, 2, 1)):
+            zz = int.from_bytes(rng.bytes(32), "big") % FP_P or 1
+            cases.append((_proj(a, zz, mags), _aff_add(a, a)))
+            cases.append((_proj(a, zz, mags, yneg=True), _aff_add(_aff_neg(a), _aff_neg(a))))
+    cases = cases[: len(cases) // 64 * 64]
+    assert len(cases) >= 256 and sum(1 for c in cases if c[1] is None) >= 8
+    out = run("pt_double", [a for a, _ in cases]).tolist()
+    for j, (_, want) in enumerate(cases):
+        _check_point_out(out[j], want, (2, 2, 1), ("pt_double", j))
+
+
 LANE_CHECKS = {
     "fe_mul": check_fe_mul,
     "fe_sq": check_fe_sq,
@@ -417,6 +712,13 @@ LANE_CHECKS = {
     "sha512_prefixed_16": lambda run: check_sha512(run, 16),
     "sha512_prefixed_8": lambda run: check_sha512(run, 8),
     "keccak_f1600": check_keccak,
+    "ristretto_decode": check_ristretto_decode,
+    "fe_sqrt_ratio_m1": check_sqrt_ratio_m1,
+    "secp_parse_pubkey": check_secp_parse_pubkey,
+    "secp_sig_scalars": check_secp_sig_scalars,
+    "secp_x_is_r": check_secp_x_is_r,
+    "pt_add": check_pt_add,
+    "pt_double": check_pt_double,
 }
 
 

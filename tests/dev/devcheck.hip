@@ -1,9 +1,12 @@
 // Stand-alone checker of the device-only code paths: the product headers'
 // __HIP_DEVICE_COMPILE__ branches, the DevRow inline-asm products and row
 // moves (row_dev.h) and the DevQuad / DevOct DPP blocks (devtables.h), one
-// small kernel per primitive. It links nothing of libcmtverify.so and holds
-// no verdict logic: tests/test_device_primitives_gpu.py builds the cases,
-// and compares the raw results with Python integers.
+// small kernel per primitive, and the verdicts' rejection rules one function
+// at a time (ristretto_decode, fe_sqrt_ratio_m1: sr25519.h; secp_parse_pubkey,
+// secp_sig_scalars, secp_x_is_r, pt_add, pt_double: secp256k1.h). It links
+// nothing of libcmtverify.so and holds no verdict logic of its own:
+// tests/test_device_primitives_gpu.py builds the cases, and compares the raw
+// results with Python integers.
 //
 //   devcheck <op>
 //   stdin:  u32 n, u32 blob_bytes, n x IN u32 (one record per thread, or per
@@ -39,6 +42,8 @@
 #include "../../cometbft_amd/csrc/quad.h"
 #include "../../cometbft_amd/csrc/oct.h"
 #include "../../cometbft_amd/csrc/row.h"
+#include "../../cometbft_amd/csrc/sr25519.h"
+#include "../../cometbft_amd/csrc/secp256k1.h"
 #ifndef DEVCHECK_HOST
 #include "../../cometbft_amd/csrc/row_dev.h"
 #include "../../cometbft_amd/csrc/devtables.h"
@@ -203,6 +208,97 @@ DC_OP(op_keccak, 50, 50, 64, 1) {
     o[2 * i] = (uint32_t)a[i];
     o[2 * i + 1] = (uint32_t)(a[i] >> 32);
   }
+}
+
+// ---- the verdicts' rejection rules (sr25519.h, secp256k1.h) ---------------------------
+static DC_FN void st_fe_bytes(uint32_t* o, const fe& f) {
+  uint32_t s[8];
+  fe_tobytes(s, f);
+  for (int i = 0; i < 8; i++) o[i] = s[i];
+}
+// in: the encoding's 8 words. out: verdict, canonical X, Y, T
+DC_OP(op_ristretto_decode, 8, 25, 64, 1) {
+  uint32_t w[8];
+  for (int i = 0; i < 8; i++) w[i] = in[i];
+  ge_p3 h;
+  o[0] = ristretto_decode(h, w) ? 1u : 0u;
+  st_fe_bytes(o + 1, h.X);
+  st_fe_bytes(o + 9, h.Y);
+  st_fe_bytes(o + 17, h.T);
+}
+// in: u, v (carried limbs). out: was_square, canonical r
+DC_OP(op_sqrt_ratio_m1, 20, 9, 64, 1) {
+  fe u, v, r;
+  ld_fe(u, in);
+  ld_fe(v, in + 10);
+  o[0] = fe_sqrt_ratio_m1(r, u, v) ? 1u : 0u;
+  st_fe_bytes(o + 1, r);
+}
+static DC_FN void ld_fp(fp& f, const uint32_t* p) {
+  for (int i = 0; i < 10; i++) f.v[i] = p[i];
+}
+static DC_FN void st_fp_words(uint32_t* o, fp a) {
+  uint32_t w[8];
+  fp_normalize(a);
+  fp_to_words(w, a);
+  for (int i = 0; i < 8; i++) o[i] = w[i];
+}
+// in: the key's 33 bytes in 9 words. out: verdict, x, y normalised
+DC_OP(op_secp_parse_pubkey, 9, 17, 64, 1) {
+  uint8_t pk[33];
+  for (int i = 0; i < 33; i++) pk[i] = (uint8_t)(in[i >> 2] >> (8 * (i & 3)));
+  pt256 q;
+  o[0] = secp_parse_pubkey(q, pk) ? 1u : 0u;
+  st_fp_words(o + 1, q.X);
+  st_fp_words(o + 9, q.Y);
+}
+// in: the signature's 64 bytes. out: verdict, r, s
+DC_OP(op_secp_sig_scalars, 16, 17, 64, 1) {
+  uint8_t sig[64];
+  for (int i = 0; i < 64; i++) sig[i] = (uint8_t)(in[i >> 2] >> (8 * (i & 3)));
+  scn r, s;
+  o[0] = secp_sig_scalars(r, s, sig) ? 1u : 0u;
+  for (int i = 0; i < 8; i++) {
+    o[1 + i] = r.v[i];
+    o[9 + i] = s.v[i];
+  }
+}
+static DC_FN void ld_pt(pt256& p, const uint32_t* in) {
+  ld_fp(p.X, in);
+  ld_fp(p.Y, in + 10);
+  ld_fp(p.Z, in + 20);
+}
+// the raw limbs of X, Y, Z, then fp_within(X, mx) | fp_within(Y, my) << 1 | fp_within(Z, mz) << 2
+static DC_FN void st_pt(uint32_t* o, const pt256& p, uint32_t mx, uint32_t my, uint32_t mz) {
+  for (int i = 0; i < 10; i++) {
+    o[i] = p.X.v[i];
+    o[10 + i] = p.Y.v[i];
+    o[20 + i] = p.Z.v[i];
+  }
+  o[30] = (fp_within(p.X, mx) ? 1u : 0u) | (fp_within(p.Y, my) ? 2u : 0u) | (fp_within(p.Z, mz) ? 4u : 0u);
+}
+// in: the accumulator's limbs (X, Y, Z), r (8 words, below n). out: secp_x_is_r
+DC_OP(op_secp_x_is_r, 38, 1, 64, 1) {
+  pt256 acc;
+  ld_pt(acc, in);
+  scn r;
+  for (int i = 0; i < 8; i++) r.v[i] = in[30 + i];
+  o[0] = secp_x_is_r(acc, r) ? 1u : 0u;
+}
+// in: p, q limbs. out: p + q limbs, its magnitudes within (3, 2, 2)
+DC_OP(op_pt_add, 60, 31, 64, 1) {
+  pt256 p, q, r;
+  ld_pt(p, in);
+  ld_pt(q, in + 30);
+  pt_add(r, p, q);
+  st_pt(o, r, 3, 2, 2);
+}
+// in: p limbs. out: 2 p limbs, its magnitudes within (2, 2, 1)
+DC_OP(op_pt_double, 30, 31, 64, 1) {
+  pt256 p, r;
+  ld_pt(p, in);
+  pt_double(r, p);
+  st_pt(o, r, 2, 2, 1);
 }
 
 #ifndef DEVCHECK_HOST
@@ -503,6 +599,13 @@ int main(int argc, char** argv) {
   DC_CASE("half", op_half);
   DC_CASE("hs_prims", op_hs_prims);
   DC_CASE("keccak", op_keccak);
+  DC_CASE("ristretto_decode", op_ristretto_decode);
+  DC_CASE("sqrt_ratio_m1", op_sqrt_ratio_m1);
+  DC_CASE("secp_parse_pubkey", op_secp_parse_pubkey);
+  DC_CASE("secp_sig_scalars", op_secp_sig_scalars);
+  DC_CASE("secp_x_is_r", op_secp_x_is_r);
+  DC_CASE("pt_add", op_pt_add);
+  DC_CASE("pt_double", op_pt_double);
   if (!strcmp(op, "sha512_16")) return drive<op_sha512<16>>(true);
   if (!strcmp(op, "sha512_8")) return drive<op_sha512<8>>(true);
 #ifndef DEVCHECK_HOST

@@ -28,6 +28,13 @@ Categories:
                   n-lambda}, 64 honest signatures each: all VALID; windowed and
                   comb accumulators meet table entries equal to themselves or
                   to their negatives under these keys
+  infinity        keys Q = [-e / r]G for a chosen r and message: [u1]G + [u2]Q is
+                  the point at infinity for every s. Invalid, and VALID for a
+                  verifier that compares X = r Z without the Z != 0 test
+                  (secp256k1_ref.verify_without_z_test; both asserted here and
+                  in tests/test_secp256k1_oracle.py). r = 1, 5, p - n - 1 (the
+                  last with r + n < p), p - n, n - 1, bytes n + 5 and random;
+                  s = (n - 1) / 2, one below it, 1 and random; both key parities
 The vectors are then shuffled with a fixed seed, so valid and invalid lanes
 share wavefronts.
 
@@ -49,7 +56,7 @@ LENGTHS = [0, 1, 55, 56, 63, 64, 65, 119, 120, 127, 128, 300]
 EXCEPTIONAL_D = [1, 2, 3, S.N - 1, S.N - 2, S.N - 3, S.LAMBDA, S.N - S.LAMBDA]
 VALID_CATS = {"honest", "reduce_quirk", "x_ge_n", "exceptional"}
 INVALID_CATS = {"flip_r", "flip_s", "flip_msg", "flip_pkx", "high_s", "r_zero", "s_zero", "r_is_n", "s_is_n",
-                "r_max", "s_max", "x_ge_n_twin", "key_prefix", "key_x_ge_p", "key_off_curve", "key_parity"}
+                "r_max", "s_max", "x_ge_n_twin", "key_prefix", "key_x_ge_p", "key_off_curve", "key_parity", "infinity"}
 
 
 def b32(x: int) -> bytes:
@@ -145,11 +152,29 @@ def build() -> dict:
             m = b"exceptional %d " % i + rng.randbytes(i % 24)
             add("exceptional", pk, m, S.sign(priv, m))
 
+    # [u1]G + [u2]Q = infinity: the signer picks r and the message and takes the
+    # private key d = -e / r, so u1 + u2 d = (e + r d) / s = 0 for any s
+    irng = random.Random(SEED + 1)  # its own stream: the vectors above stay what they were
+    inf_r = [1, 5, S.P - S.N - 1, S.P - S.N, S.N - 1, S.N + 5] + [irng.randrange(1, S.N) for _ in range(6)]
+    inf_s = [S.HALF_N, S.HALF_N - 1, 1]
+    parities = set()
+    for i, r in enumerate(inf_r):
+        m = b"infinity %d " % i + irng.randbytes(LENGTHS[i % len(LENGTHS)])
+        d = -S.msg_scalar(m) * pow(r % S.N, S.N - 2, S.N) % S.N
+        pk = S.pubkey_from_priv(b32(d))
+        parities.add(pk[0])
+        s = inf_s[i] if i < len(inf_s) else irng.randrange(1, S.HALF_N)
+        add("infinity", pk, m, b32(r) + b32(s))
+    assert parities == {2, 3} and any(r + S.N < S.P for r in inf_r)
+
     rng.shuffle(vecs)
     for v in vecs:
         v["valid"] = int(S.verify(bytes.fromhex(v["pk"]), bytes.fromhex(v["msg"]), bytes.fromhex(v["sig"])))
         assert v["valid"] == (v["cat"] in VALID_CATS), v
         assert v["cat"] in VALID_CATS | INVALID_CATS
+        if v["cat"] == "infinity":  # discriminating: only the Z != 0 test rejects it
+            assert S.verify_without_z_test(bytes.fromhex(v["pk"]), bytes.fromhex(v["msg"]), bytes.fromhex(v["sig"])), v
+    assert len(vecs) % 64 != 0  # the GPU tests' last bitmap word stays ragged
     summary = {}
     for v in vecs:
         s = summary.setdefault(v["cat"], {"n": 0, "valid": 0})

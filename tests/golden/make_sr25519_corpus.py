@@ -20,6 +20,34 @@ Categories:
   identity_pk     the all-zero key (the identity) with s = r: valid
   rfc_bad         RFC 9496 A.2-style invalid encodings as pk and as R
   random          random bytes
+  decode_pk, decode_r
+                  one ristretto255 decode rule each ("rule"), as the key and as
+                  R: the strict verdict is invalid and the verdict of a verifier
+                  WITHOUT that one rule (oracle/sr25519_ref.py verify_lenient)
+                  is valid; both are asserted here and again from the JSON in
+                  tests/test_sr25519_oracle.py. The pk_encoding / r_encoding /
+                  rfc_bad vectors pair a bad encoding with a signature made for
+                  other bytes, so the challenge changes and any decoder rejects
+                  them; these are signed over the alternative encoding e itself
+                  by a signer who knows the log a of the point e decodes to
+                  without the rule (key: transcript over e, s = r + k a; R: e in
+                  the transcript and the signature):
+                    canonical   p (the identity's ed ff .. 7f; of s + p, s < 19,
+                                the only one in a coset with a known log), and
+                                bit 255 set on an honest encoding
+                    nonneg_s    p - s (odd)
+                    nonneg_t    the coset's other even representatives among
+                                1/s, -1/s and those times sqrt(-1) that decode
+                                with t negative
+                    nonzero_y   s = p - 1 (ec ff .. 7f): a point of order 4, in
+                                the identity's coset
+                  was_square has no such vector: without the rule a non-square
+                  encoding gives coordinates off the curve, on which the
+                  addition formulas are no group law, and was_square_search
+                  finds none of its candidates (even s < 1000, RFC_BAD) accepted
+                  under the two signatures that need no discrete log. The rule
+                  is pinned at the primitive (tests/dev/devcases.py
+                  check_ristretto_decode).
 
     python tests/golden/make_sr25519_corpus.py [--out tests/golden/sr25519_corpus.json]
 """
@@ -41,6 +69,7 @@ from oracle import signbytes as SB  # noqa: E402
 
 SEED = 25519
 P, L = S.P, S.L
+PINNED_RULES = ("canonical", "nonneg_s", "nonneg_t", "nonzero_y")  # by decode_pk / decode_r vectors
 
 RISTRETTO_MULTIPLES = [  # RFC 9496 appendix A.1: encodings of [i]B, i = 0..8
     "0000000000000000000000000000000000000000000000000000000000000000",
@@ -94,6 +123,98 @@ def vote_msgs(rng: random.Random):
         bid = None if nil else (hashlib.sha256(b"block%d" % h).digest(), 1, hashlib.sha256(b"parts%d" % h).digest())
         out.append(SB.vote_sign_bytes(chain, 2, h, rnd, bid, 1672531200 + h, rng.randrange(10**9)))
     return out
+
+
+def alternative_encodings(xs):
+    """[(rule, e, log)]: 32-byte strings e the strict decoder rejects and the
+    decoder without `rule` (alone) maps into the coset of [log]B, for log = x
+    or -x, x in xs; log = 0 stands for the identity's coset E[4]."""
+    out = []
+    inv = lambda v: pow(v, P - 2, P)  # noqa: E731
+
+    def keep(rule, v, x):
+        e = v.to_bytes(32, "little")
+        pt = S.ristretto_decode_lenient(e, (rule,))
+        if S.ristretto_decode(e) is not None or pt is None:
+            return False
+        for log in (x, (L - x) % L):  # 1/s lands in the coset of -[x]B
+            if S.ristretto_equal(pt, S.scalar_mult(log, S.B)):
+                out.append((rule, e, log))
+                return True
+        return False
+
+    # non-canonical s + p, s < 19: only those that land in E[4] have a known log
+    for s in range(0, 19):
+        keep("canonical", s + P, 0)
+    keep("nonzero_y", P - 1, 0)  # s = -1: canonical, even, square, t = 0, y = 0, order 4
+    for x in xs:
+        c = int.from_bytes(S.ristretto_encode(S.scalar_mult(x, S.B)), "little")
+        assert keep("canonical", c | (1 << 255), x)  # bit 255 set
+        assert keep("nonneg_s", P - c, x)            # negative
+        # the coset's other representatives: 1/s, -1/s and those times sqrt(-1)
+        found = 0
+        for v in (inv(c), -inv(c), c * S.SQRT_M1, -c * S.SQRT_M1, inv(c) * S.SQRT_M1, -inv(c) * S.SQRT_M1):
+            v %= P
+            if v & 1 == 0:  # the odd ones break nonneg_s as well: not discriminating
+                found += keep("nonneg_t", v, x)
+        assert found, x
+    return out
+
+
+def was_square_search(rng):
+    """Whether any non-square encoding is accepted by a verifier without the
+    was_square rule, under the two signatures that need no discrete log: the
+    identity-style one (s = r, R = [r]B) for the key, and s = k a for R."""
+    cands = [v.to_bytes(32, "little") for v in range(0, 1000, 2)] + [bytes.fromhex(h) for h in RFC_BAD]
+    cands = [e for e in cands if S.ristretto_decode_lenient(e, ()) is None
+             and S.ristretto_decode_lenient(e, ("was_square",)) is not None]
+    hits = []
+    mini = bytes(range(32))
+    a, _ = S.expand_mini(mini)
+    pk = S.pubkey_from_mini(mini)
+    for e in cands:
+        r = rng.randrange(1, L)
+        Rb = S.ristretto_encode(S.scalar_mult(r, S.B))
+        if S.verify_lenient(e, b"m", S.sign_encoded(0, r, b"m", e, Rb), skip_pk=("was_square",)):
+            hits.append(("pk", e.hex()))
+        if S.verify_lenient(pk, b"m", S.sign_encoded(a, 0, b"m", pk, e), skip_r=("was_square",)):
+            hits.append(("r", e.hex()))
+    return len(cands), hits
+
+
+def lenient_decode_vectors(minis, msgs):
+    """The decode_pk / decode_r vectors: for every alternative encoding e of a
+    point with a known log, a signature whose transcript runs over e. Key: the
+    signer of A = [a]B presents e, R = [r]B, s = r + k a. R: the signature
+    carries e_R for R = [r]B. Each dict also names the rule and carries no
+    verdict yet."""
+    rng = random.Random(SEED + 1)
+    scal = [S.expand_mini(m)[0] for m in minis[:3]]
+    alts = alternative_encodings(scal)
+    # a CanonicalVote, the lengths around the STROBE block end (R = 166), short and long
+    pick = [msgs[0]] + [m for m in msgs if len(m) in (165, 166, 167, 0, 300)]
+    assert {165, 166, 167} <= {len(m) for m in pick}
+    out = []
+    for j, (rule, e, x) in enumerate(alts):
+        for where, t in (("pk", 0), ("r", 0), ("pk", 1), ("r", 1)):
+            m = pick[(2 * j + t + 3 * (where == "r")) % len(pick)]
+            other = rng.randrange(1, L)  # the honest side's scalar
+            if where == "pk":
+                pkb, a, r = e, x, other
+                Rb = S.ristretto_encode(S.scalar_mult(r, S.B))
+            else:
+                a, r, Rb = other, x, e
+                pkb = S.ristretto_encode(S.scalar_mult(a, S.B))
+            out.append({"cat": "decode_" + where, "rule": rule, "pk": pkb.hex(), "msg": m.hex(),
+                        "sig": S.sign_encoded(a, r, m, pkb, Rb).hex()})
+    return out
+
+
+def lenient_verdict(v) -> bool:
+    """The verdict of the verifier without v's rule on v's side (decode_pk /
+    decode_r vectors)."""
+    skip = {"skip_pk" if v["cat"] == "decode_pk" else "skip_r": (v["rule"],)}
+    return S.verify_lenient(bytes.fromhex(v["pk"]), bytes.fromhex(v["msg"]), bytes.fromhex(v["sig"]), **skip)
 
 
 def main():
@@ -165,10 +286,19 @@ def main():
     for _ in range(16):
         add("random", bytes(rng.randrange(256) for _ in range(32)), msgs[rng.randrange(len(msgs))],
             bytes(rng.randrange(256) for _ in range(64)))
+    vecs += lenient_decode_vectors(minis, msgs)
 
     # verdicts: Python restatement, cross-checked against the C restatement
     for v in vecs:
         v["valid"] = int(S.verify(bytes.fromhex(v["pk"]), bytes.fromhex(v["msg"]), bytes.fromhex(v["sig"])))
+        if "rule" in v:  # discriminating: the strict verdict and the one without the rule differ
+            assert v["valid"] == 0 and lenient_verdict(v), v
+    pinned = {(v["cat"], v["rule"]) for v in vecs if "rule" in v}
+    assert pinned == {(c, r) for c in ("decode_pk", "decode_r") for r in PINNED_RULES}, pinned
+    n_nonsquare, hits = was_square_search(random.Random(SEED + 2))
+    print("was_square_search:", n_nonsquare, "non-square candidates,", len(hits), "accepted")
+    assert n_nonsquare >= 64 and not hits, hits
+    assert len(vecs) % 64 != 0  # the GPU tests' last bitmap word stays ragged
     pk = np.array([np.frombuffer(bytes.fromhex(v["pk"]), np.uint8) for v in vecs])
     sig = np.array([np.frombuffer(bytes.fromhex(v["sig"]), np.uint8) for v in vecs])
     m, off = C.pack_msgs([bytes.fromhex(v["msg"]) for v in vecs])

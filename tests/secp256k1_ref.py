@@ -161,6 +161,25 @@ def verify(pk: bytes, msg: bytes, sig: bytes) -> bool:
     return to_affine(x)[0] % N == r
 
 
+def verify_without_z_test(pk: bytes, msg: bytes, sig: bytes) -> bool:
+    """The verdict of a verifier that compares X = r Z on homogeneous
+    coordinates without first rejecting Z = 0: the point at infinity (0 : 1 : 0)
+    satisfies 0 = r * 0 for every r. Everything else is verify(). Used to show
+    that the corpus's `infinity` vectors discriminate."""
+    if len(sig) != 64:
+        return False
+    q = parse_pubkey(pk)
+    if q is None:
+        return False
+    r = int.from_bytes(sig[:32], "big") % N
+    s = int.from_bytes(sig[32:], "big") % N
+    if r == 0 or s == 0 or s > HALF_N:
+        return False
+    w = pow(s, N - 2, N)
+    x = jadd(gmul(msg_scalar(msg) * w % N), jmul(r * w % N, q))
+    return x is None or to_affine(x)[0] % N == r
+
+
 def sign(priv: bytes, msg: bytes, seed: bytes = b"") -> bytes:
     """A deterministic lower-S signature (the nonce is a hash of the key, the
     message, the seed and a counter; not RFC 6979, which the verdict does not

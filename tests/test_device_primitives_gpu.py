@@ -37,7 +37,14 @@ this file came after):
       fails test_lane_primitive[hs_udiv31_clz] (and the host check) only:
       the decomposition's output does not change (Lehmer's corner check
       rejects the quotient, the exact Euclid steps give the same pair).
-      Before: no CPU test failed; the GPU tests were not run against it."""
+      Before: no CPU test failed; the GPU tests were not run against it.
+
+The verdicts' rejection rules as primitives (test_lane_primitive[ristretto_decode,
+fe_sqrt_ratio_m1, secp_parse_pubkey, secp_sig_scalars, secp_x_is_r, pt_add,
+pt_double]): each rule of sr25519.h's ristretto_decode and of secp256k1.h's
+key parser, scalar checks and final comparison, removed alone on a CPU host
+build, fails one of them or a corpus test; was_square, r = 0 and `wraps` in
+secp_x_is_r are pinned by these alone. The table is DESIGN.md section 2.1."""
 import pytest
 
 from tests.dev import devbuild, devcases

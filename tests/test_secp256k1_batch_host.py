@@ -5,7 +5,7 @@ secp_verify_keyed_batch_lane<KB> (the function
 k_verify_secp256k1_keyed_batch<KB> calls: KB signatures per lane sharing one
 inversion mod n) laid out as the kernel lays signatures out over its lanes.
 
-  * the registered-key corpus (764 vectors, 83 keys) in two fixed
+  * the registered-key corpus (776 vectors, 95 keys) in two fixed
     permutations, KB = 4 and 8: every verdict equals secp_verify_keyed_one's
     and the corpus's, and every invalid category shares a lane with a valid
     signature
@@ -85,7 +85,7 @@ def assert_corpus(binary, corpus, kb, seed):
 
 @pytest.mark.parametrize("kb", KBS)
 def test_corpus_two_permutations(check, corpus, kb):
-    assert len(corpus[1]) == 764 and len(corpus[0]) == 83
+    assert len(corpus[1]) == 776 and len(corpus[0]) == 95
     for seed in (0xB47C4, 0xB47C8):
         assert_corpus(check, corpus, kb, seed)
 

@@ -90,10 +90,10 @@ def check_bitmap(words, exp):
 
 def test_corpus_bit_exact(gpu_ctx):
     pks, idx, vecs = V.corpus_indexed()
-    assert len(vecs) == 764 and len(pks) == 83
+    assert len(vecs) == 776 and len(pks) == 95
     ks = gpu_ctx.register_secp256k1_keys(key_array(pks))
     try:
-        assert len(ks) == 83
+        assert len(ks) == 95
         sig = np.array([np.frombuffer(bytes.fromhex(v["sig"]), np.uint8) for v in vecs])
         m, off = pack_messages([bytes.fromhex(v["msg"]) for v in vecs])
         exp = np.array([v["valid"] for v in vecs], np.uint8)

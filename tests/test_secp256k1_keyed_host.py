@@ -135,7 +135,7 @@ def assert_corpus(binary, corpus):
 
 def test_corpus_bit_exact(check, corpus):
     keys, _, vecs = corpus
-    assert len(vecs) == 764 and len(keys) == 83
+    assert len(vecs) == 776 and len(keys) == 95
     assert sum(v["cat"] == "exceptional" for v in vecs) == 512
     assert_corpus(check, corpus)
 

@@ -95,6 +95,32 @@ def test_every_category_present_with_its_verdict(corpus_doc):
         assert 0 < sum(valid[64 * w: 64 * w + 64]) < 64, w
 
 
+def test_infinity_vectors_discriminate(corpus_doc):
+    """[u1]G + [u2]Q is the point at infinity in every `infinity` vector:
+    rejected by the oracle, accepted by the verifier without the Z != 0 test
+    (X = 0 = r * 0), both recomputed from the committed JSON; several r, one of
+    them with r + n < p, both key parities, s at and below (n - 1) / 2."""
+    vecs = [v for v in corpus_doc["vectors"] if v["cat"] == "infinity"]
+    assert len(vecs) >= 8
+    rs, ss = set(), set()
+    for v in vecs:
+        pk, msg, sig = bytes.fromhex(v["pk"]), bytes.fromhex(v["msg"]), bytes.fromhex(v["sig"])
+        r, s = int.from_bytes(sig[:32], "big") % S.N, int.from_bytes(sig[32:], "big")
+        w = pow(s, S.N - 2, S.N)
+        assert S.jadd(S.gmul(S.msg_scalar(msg) * w), S.jmul(r * w, S.parse_pubkey(pk))) is None
+        assert v["valid"] == 0 and not S.verify(pk, msg, sig) and S.verify_without_z_test(pk, msg, sig), v
+        rs.add(r)
+        ss.add(s)
+    assert len(rs) >= 8 and any(r + S.N < S.P for r in rs) and any(r + S.N >= S.P for r in rs)
+    assert {S.HALF_N, S.HALF_N - 1} <= ss and max(ss) == S.HALF_N
+    assert {v["pk"][:2] for v in vecs} == {"02", "03"}
+    # the lenient verifier is the oracle everywhere else
+    for v in corpus_doc["vectors"][::9]:
+        if v["cat"] != "infinity":
+            args = bytes.fromhex(v["pk"]), bytes.fromhex(v["msg"]), bytes.fromhex(v["sig"])
+            assert S.verify_without_z_test(*args) == bool(v["valid"])
+
+
 def test_constructed_edge_vectors(corpus_doc):
     """The constructed vectors are what their categories say: byte values at
     or above n in reduce_quirk, a nonce point with x in [n, p) in x_ge_n."""

@@ -95,6 +95,40 @@ def test_c_oracle_matches_corpus(vectors):
     assert np.array_equal(got, vectors["valid"])
 
 
+def test_decode_vectors_discriminate(doc):
+    """Every decode_pk / decode_r vector is rejected by the strict oracle and
+    accepted by the verifier without that vector's one rule on that side, both
+    recomputed here from the committed JSON: a kernel that dropped the rule
+    would accept it. Each rule of ristretto_decode but was_square (pinned at the
+    primitive: tests/dev/devcases.py check_ristretto_decode) has such vectors
+    for the key and for R, on both sides of the STROBE block end and over a
+    CanonicalVote."""
+    vecs = [v for v in doc["vectors"] if v["cat"] in ("decode_pk", "decode_r")]
+    seen = {}
+    for v in vecs:
+        pk, msg, sig = bytes.fromhex(v["pk"]), bytes.fromhex(v["msg"]), bytes.fromhex(v["sig"])
+        skip = {"skip_pk" if v["cat"] == "decode_pk" else "skip_r": (v["rule"],)}
+        assert v["valid"] == 0 and not S.verify(pk, msg, sig), v
+        assert S.verify_lenient(pk, msg, sig, **skip), v
+        # the rule's side is the only thing wrong: the other side decodes strictly
+        assert S.ristretto_decode(sig[:32] if v["cat"] == "decode_pk" else pk) is not None, v
+        seen.setdefault((v["cat"], v["rule"]), set()).add(len(msg))
+    rules = {"canonical", "nonneg_s", "nonneg_t", "nonzero_y"}
+    assert set(seen) == {(c, r) for c in ("decode_pk", "decode_r") for r in rules}
+    lens = set().union(*seen.values())
+    assert {165, 166, 167} <= lens and 117 in lens  # 117: the CanonicalVote of the corpus
+    bit255 = [v for v in vecs if v["rule"] == "canonical" and bytes.fromhex(v["pk"] if v["cat"] == "decode_pk"
+                                                                                else v["sig"][:64])[31] & 0x80]
+    assert {v["cat"] for v in bit255} == {"decode_pk", "decode_r"}
+
+
+def test_lenient_decoder_with_no_rule_skipped_is_the_strict_one(doc):
+    encs = {bytes.fromhex(v[k])[:32] for v in doc["vectors"] for k in ("pk", "sig")}
+    assert len(encs) >= 200
+    for e in encs:
+        assert S.ristretto_decode_lenient(e, ()) == S.ristretto_decode(e), e.hex()
+
+
 def test_corpus_covers_the_equality_path(vectors):
     """Honest signatures where R' != R as points but R' == R as ristretto
     elements (they differ by 4-torsion): an exact point comparison would

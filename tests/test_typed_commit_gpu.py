@@ -221,7 +221,7 @@ def test_secp_light_trusting(gpu_ctx, cache_ctx, cached):
     assert check("trusting", ctx, vals, chain, stray)[0] == "not_enough_power"
 
 
-SECP_BAD = ["zero_sec", "zero_nanos", "high_s", "sig63", "prefix4", "off_curve", "key32"]
+SECP_BAD = ["zero_sec", "zero_nanos", "high_s", "sig63", "prefix4", "off_curve", "key32", "infinity"]
 
 
 @pytest.mark.parametrize("cached", [False, True], ids=["nocache", "cache"])
@@ -246,6 +246,15 @@ def test_secp_signature_and_key_cases(gpu_ctx, cache_ctx, case, cached):
         commit = with_sig(good, i, high_s(good[3][i].signature))
     elif case == "sig63":
         commit = with_sig(good, i, good[3][i].signature[:63])
+    elif case == "infinity":
+        # the key [-e / r]G: [u1]G + [u2]Q is the point at infinity, which
+        # X = r Z alone accepts (0 = r * 0); r + n < p
+        msg, r = R.sign_bytes(chain, HEIGHT, 0, good[2], good[3][i]), 5
+        d = -SECP.msg_scalar(msg) * pow(r, SECP.N - 2, SECP.N) % SECP.N
+        pk, sig = SECP.pubkey_from_priv(d.to_bytes(32, "big")), r.to_bytes(32, "big") + SECP.HALF_N.to_bytes(32, "big")
+        assert SECP.verify_without_z_test(pk, msg, sig) and not SECP.verify(pk, msg, sig)
+        vals = vals[:i] + [R.Val("secp256k1", pk, vals[i].power, vals[i].secret)] + vals[i + 1:]
+        commit = with_sig(good, i, sig)
     else:
         pk = vals[i].pub_key
         if case == "prefix4":
@@ -271,11 +280,26 @@ def sr_case():
     return vals, R.make_commit(vals, "sr-chain", HEIGHT)
 
 
-@pytest.mark.parametrize("case", ["good", "flipped", "key31"])
+@pytest.mark.parametrize("case", ["good", "flipped", "key31", "bit255", "negative_r"])
 def test_sr25519_set(gpu_ctx, sr_case, case):
     vals, commit = sr_case
     if case == "flipped":
         commit = with_sig(commit, 33, flipped(commit[3][33].signature))
+    if case in ("bit255", "negative_r"):
+        # validator 9 presents another encoding of its key (bit 255 set), or of
+        # R (p - s), and signs over those bytes: only the decoder's canonical /
+        # non-negative rule makes the signature wrong
+        msg = R.sign_bytes("sr-chain", HEIGHT, 0, commit[2], commit[3][9])
+        a, r = R.SR.expand_mini(vals[9].secret)[0], 12345678901234567890
+        pk, rb = vals[9].pub_key, R.SR.ristretto_encode(R.SR.scalar_mult(r, R.SR.B))
+        if case == "bit255":
+            pk, skip = pk[:31] + bytes([pk[31] | 0x80]), {"skip_pk": ("canonical",)}
+            vals = vals[:9] + [R.Val("sr25519", pk, vals[9].power)] + vals[10:]
+        else:
+            rb, skip = (R.SR.P - int.from_bytes(rb, "little")).to_bytes(32, "little"), {"skip_r": ("nonneg_s",)}
+        sig = R.SR.sign_encoded(a, r, msg, pk, rb)
+        assert R.SR.verify_lenient(pk, msg, sig, **skip) and not R.SR.verify(pk, msg, sig)
+        commit = with_sig(commit, 9, sig)
     if case == "key31":  # zero-padded to 32 bytes: another key, so the signature is wrong
         vals = vals[:9] + [R.Val("sr25519", vals[9].pub_key[:31], vals[9].power)] + vals[10:]
     got = check("full", gpu_ctx, vals, "sr-chain", commit)

@@ -218,10 +218,26 @@ def scenario(name):
         return hs
     if name == "single":
         return a(70, 1)
+    if name == "decode_rule":
+        # an sr25519 validator of a mixed set presents its key with bit 255 set;
+        # at the second height its signature is made over those very bytes, so
+        # only the decoder's canonical rule makes it wrong
+        vals = list(vset(MIXED_T, 200, 20))
+        v = vals[6]
+        pk = v.pub_key[:31] + bytes([v.pub_key[31] | 0x80])
+        vals[6] = R.Val("sr25519", pk, v.power, v.secret)
+        hs = [(tuple(vals), h, R.make_commit(vals, CHAIN, h)) for h in (90, 91)]
+        msg = R.sign_bytes(CHAIN, 91, 0, hs[1][2][2], hs[1][2][3][6])
+        a_log, r = R.SR.expand_mini(v.secret)[0], 98765432109876543210
+        sig = R.SR.sign_encoded(a_log, r, msg, pk, R.SR.ristretto_encode(R.SR.scalar_mult(r, R.SR.B)))
+        assert v.key_type == "sr25519" and not R.SR.verify(pk, msg, sig)
+        assert R.SR.verify_lenient(pk, msg, sig, skip_pk=("canonical",))
+        hs[1] = with_sig(hs[1], 6, sig)
+        return hs
     raise KeyError(name)
 
 
-SCENARIOS = ("one_set", "two_sets", "mixed_between", "wrong_height", "wrong_sigs", "single")
+SCENARIOS = ("one_set", "two_sets", "mixed_between", "wrong_height", "wrong_sigs", "single", "decode_rule")
 
 
 @pytest.mark.parametrize("kind", ("full", "light", "trusting"))
@@ -231,6 +247,8 @@ def test_equals_per_height_loop_and_reference(plain_ctx, cache_ctx, name, kind):
     want = ref(kind, hs)
     if name == "wrong_sigs" and kind == "full":
         assert [w and w[2] for w in want] == [None, 5, 14, 8, None, 19]
+    if name == "decode_rule":  # every loop reaches validator 6
+        assert [w and w[2] for w in want] == [6, 6]
     if name == "wrong_height" and kind != "trusting":
         assert [w and w[0] for w in want] == [None, None, "height", None, None]
     for ctx in (plain_ctx, cache_ctx):
@@ -297,16 +315,26 @@ def kb_for(n, min_waves):
     return kb if kb >= 4 else 1
 
 
+INF_IDX = 12  # batched_heights' validator whose signature at the fourth height sums to infinity
+
+
 @lru_cache(maxsize=None)
 def batched_heights(n_heights, n_vals):
     """All votes for the block; the last validator holds a key the parser
     rejects (every height's last signature is wrong); a flipped signature, an
     s = 0, an s = n and a high-S twin at different indices of different
-    heights, the twin in a height with a later flipped signature."""
+    heights, the twin in a height with a later flipped signature. With more
+    than three heights, validator 12's private key is -e / r for its own
+    message e of the fourth height and r = 5: it signs honestly everywhere
+    else, and its (r, s) there makes [u1]G + [u2]Q the point at infinity."""
     good = list(R.make_vals(["secp256k1"] * n_vals, start=400))
     last = good[-1]
     good[-1] = R.Val("secp256k1", bytes([5]) + last.pub_key[1:], last.power, last.secret)
     assert SECP.parse_pubkey(good[-1].pub_key) is None
+    if n_heights > 3:
+        msg = R.sign_bytes(CHAIN, 503, 0, R.block_id_for(503), R.Sig(R.COMMIT, b"", R.timestamp_for(INF_IDX)))
+        d = (-SECP.msg_scalar(msg) * pow(5, SECP.N - 2, SECP.N) % SECP.N).to_bytes(32, "big")
+        good[INF_IDX] = R.Val("secp256k1", SECP.pubkey_from_priv(d), good[INF_IDX].power, d)
     vals = tuple(good)
     hs = [(vals, h, R.make_commit(list(vals), CHAIN, h)) for h in range(500, 500 + n_heights)]
     zero_s = lambda sig: sig[:32] + bytes(32)  # noqa: E731
@@ -317,6 +345,11 @@ def batched_heights(n_heights, n_vals):
     hs[2] = with_sig(hs[2], 21, n_s(sig_of(hs[2], 21)))
     if n_heights > 3:
         hs[n_heights - 1] = with_sig(hs[n_heights - 1], 2, flipped(sig_of(hs[n_heights - 1], 2), 40))
+        inf = (5).to_bytes(32, "big") + (SECP.HALF_N - 1).to_bytes(32, "big")
+        assert SECP.verify(good[INF_IDX].pub_key, msg, sig_of(hs[3], INF_IDX))
+        assert not SECP.verify(good[INF_IDX].pub_key, msg, inf)
+        assert SECP.verify_without_z_test(good[INF_IDX].pub_key, msg, inf)
+        hs[3] = with_sig(hs[3], INF_IDX, inf)
     return tuple(hs)
 
 
@@ -328,10 +361,11 @@ def test_batched_kernel(cache_ctx, min_waves, n_heights, n_vals, kb):
     hs = list(batched_heights(n_heights, n_vals))
     # at least one lane holds an invalid and a valid signature in different rounds
     bad = {0 * n_vals + 7, 0 * n_vals + n_vals - 2, 1 * n_vals + 33, 2 * n_vals + 21} | \
-        {h * n_vals + n_vals - 1 for h in range(n_heights)}
+        {h * n_vals + n_vals - 1 for h in range(n_heights)} | ({3 * n_vals + INF_IDX} if n_heights > 3 else set())
     assert any(q not in bad and q % lanes == p % lanes for p in bad for q in range(n))
     want = ref("full", hs)
-    assert [w[2] for w in want[:3]] == [7, 33, 21] and all(w[2] == n_vals - 1 for w in want[3:-1])
+    assert [w[2] for w in want[:3]] == [7, 33, 21] and all(w[2] == n_vals - 1 for w in want[4:-1])
+    assert n_heights == 3 or want[3][2] == INF_IDX  # the infinity signature is the fourth height's first wrong one
     ctx = open_ctx(cache=4, CMTV_KEYED_BATCH_MIN_WAVES=min_waves)
     try:
         for kind in ("full", "light"):
