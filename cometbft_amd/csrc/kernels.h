@@ -20,16 +20,20 @@ constexpr uint32_t kCombScratchWordsPerKey = 128 * 320;  // prefix products whil
 //   kFormLane : one signature per lane (k_verify, k_verify_sr25519)
 //   kFormQuad : four lanes per signature, three quad waves + a helper wave
 //               that hashes and sums each window's table entries
-//               (k_verify_quad_hs, k_verify_sr25519_quad_hs)
+//               (k_verify_quad_hs_fold with a fifth wave for [s]B, or
+//               k_verify_quad_hs; k_verify_sr25519_quad_hs)
 //   kFormOct2 : eight lanes per signature in two waves (k_verify_oct_split)
 //   kFormRow  : one wave per signature, three per workgroup + a helper
 //               (k_verify_row_split)
 //   kFormRow4 : four waves per signature (k_verify_row4_split)
 // sr25519 has the lane and quad forms. kLaunchForceWide: the CMTV_FORCE_WIDE
 // test knob (every quad-family verifier takes the 64-window schedule); bits
-// 16..31: the helper-summed forms' tuning (hs_tune, CMTV_HS_PRE).
+// 16..31: the helper-summed forms' tuning (hs_tune: CMTV_HS_PRE in its bits
+// 0..7, CMTV_HS_FOLD_TUNE in bits 8..10). kLaunchHsFold: the Ed25519 quad form
+// runs k_verify_quad_hs_fold ([s]B folded into R by a fifth wave) instead of
+// k_verify_quad_hs.
 constexpr uint32_t kFormLane = 0, kFormQuad = 1, kFormOct2 = 2, kFormRow = 3, kFormRow4 = 4;
-constexpr uint32_t kFormMask = 0xFF, kLaunchForceWide = 0x100;
+constexpr uint32_t kFormMask = 0xFF, kLaunchForceWide = 0x100, kLaunchHsFold = 0x200;
 // registered-key forms (launch_verify_keyed): the keyed row kernel
 // (k_verify_keyed_row_split, one signature per workgroup), the keyed quad
 // kernel with two helper waves (k_verify_keyed_quad_split), the lane kernels
@@ -79,16 +83,22 @@ constexpr uint32_t kSbFuseMaxMsg = 192;
 // (CmtvDev::d_diag, read by cmtv_stats_get): kDiagLateK = quad waves of
 // k_verify_keyed_quad_split that stopped waiting for the hash helper and
 // hashed their own signatures. kKeyedWaitDefault = the polls before that.
-constexpr uint32_t kDiagLateK = 0, kDiagWords = 4;
-constexpr uint32_t kKeyedWaitDefault = 1u << 22;
+// kDiagLatePs = quad waves of k_verify_quad_hs_fold that stopped waiting for
+// the comb wave's [s]B and added the comb rows themselves, after kPsWaitDefault
+// polls.
+constexpr uint32_t kDiagLateK = 0, kDiagLatePs = 1, kDiagWords = 4;
+constexpr uint32_t kKeyedWaitDefault = 1u << 22, kPsWaitDefault = 1u << 22;
 
 hipError_t launch_btab_init(uint32_t* d_rows, hipStream_t s);
 // sb (may be null) is honoured by the forms whose helper wave hashes (every
 // form but kFormLane); the caller launches k_sign_bytes otherwise. The row
 // forms need row_slot (one slot of the device's ring) when bitmap is set.
+// ps_wait, diag: the folded quad form's polls for [s]B and the device's
+// diagnostic counters (may be null).
 hipError_t launch_verify(uint32_t mode, uint32_t n, const void* pk, const void* sig, const void* msg,
                          const void* off, const uint32_t* btab, uint32_t* atab, void* valid, void* bitmap,
-                         uint32_t kflags, hipStream_t s, const SbFuse* sb = nullptr, const RowSlot* row_slot = nullptr);
+                         uint32_t kflags, hipStream_t s, const SbFuse* sb = nullptr, const RowSlot* row_slot = nullptr,
+                         uint32_t ps_wait = kPsWaitDefault, uint32_t* diag = nullptr);
 hipError_t launch_comb_build(uint32_t n_keys, const void* keys_pk, uint8_t* keys_ok, uint32_t* tabs,
                              uint32_t* scratch, bool negate, hipStream_t s);
 // form: kKeyedRow (row_slot: a slot of the device's bitmap ring when bitmap

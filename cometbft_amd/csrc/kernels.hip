@@ -6,9 +6,10 @@
 //   k_verify<MODE>: one signature per lane: SHA-512 + mod-L + decompression +
 //                   Straus [s]B - [k]A + GO_STDLIB / ZIP215 final check, then a
 //                   wavefront ballot packs 64 verdicts into one bitmap word
-//   k_verify_quad_hs / k_verify_oct_split / k_verify_row_split /
-//   k_verify_row4_split<MODE>: the same with 4 / 8 / 64 / 256 lanes per
-//                   signature and a helper wave (smaller batches; kernels.h forms)
+//   k_verify_quad_hs_fold / k_verify_quad_hs / k_verify_oct_split /
+//   k_verify_row_split / k_verify_row4_split<MODE>: the same with 4 / 4 / 8 /
+//                   64 / 256 lanes per signature and a helper wave (smaller
+//                   batches; kernels.h forms)
 //
 // Memory layout (HBM):
 //   pk   : n x 32 B   (row i = 8 words, read as 2 x dwordx4)
@@ -165,6 +166,180 @@ __global__ __launch_bounds__(256, CMTV_QUAD_WAVES_PER_EU) void k_verify_quad_hs(
       });
   CMTV_STAMP(5);
   CMTV_STAMP_VAL(6, qwait);
+  quad_verdict_store(v, active, s, n, wave, t, out_valid, out_bitmap, tags);
+}
+
+// k_verify_quad_hs with [s]B folded into R (quad.h q_verify_hs_fold): a fifth
+// wave, the comb wave, runs the 16-position comb on every signature's s from
+// the first cycle, one lane per signature (BComb16Ahead; it needs no hash),
+// and publishes P_s = [s]B through an LDS flag. The quads build A's table,
+// take P_s, form P_s - R and build its table; their windows then carry no
+// fixed-base addition at all, the helper computes no u = k2 s mod L, and the
+// last barrier with its [u]B addition is gone.
+//
+// 5 waves on 4 SIMDs: wave 4 lands on wave 0's SIMD (the probe's HW_ID stamp,
+// every workgroup), so wave 0 is the hash helper and waves 1-3 are the quads.
+// The helper reaches barrier 1 some 56k cycles before the quads even with
+// the comb beside it, so the comb fills that SIMD's slack; beside a quad wave
+// the same comb costs the kernel 12%. The comb wave takes the top
+// kHsFoldCombPre positions (all 16, measured best; CMTV_HS_PRE overrides it)
+// and the quads add the rest themselves before they look at the flag.
+//
+// P_s travels as (X, Y, Z), 30 words a signature, in the tail of xbuf: the
+// sign-bytes take its first 48 x kSbFuseMaxMsg bytes and the ring is written
+// only after barrier 1, which the comb wave meets after its stores -- so a
+// comb wave that comes late harms nothing, which an entry slot of R's table
+// (rewritten by a quad wave that stopped waiting) would not allow. A quad lane
+// multiplies the two factors of its coordinate of (XZ, YZ, Z^2, XY), the same
+// point as an extended one.
+//
+// The quads poll the flag at most ps_wait times. The verdict never depends on
+// that wait: a quad wave that stops waiting adds the comb wave's rows itself
+// (q_sbase16_add) and counts itself in diag[kDiagLatePs] (cmtv_stats.
+// late_ps_waves); ps_wait = 0 (the CMTV_FORCE_PS_LATE test knob) skips the
+// comb wave's work and the flag, so every quad wave takes that path. The
+// comb wave meets barrier 1 and every window barrier (the count is in prep
+// after barrier 1) and returns with the helper. hs_tune bits 8..10
+// (CMTV_HS_FOLD_TUNE): 1 = the hash helper is wave 3 and the quads waves 0-2
+// (the comb then shares a quad's SIMD), 2 / 4 = the comb wave at issue
+// priority 0 / 3.
+template <uint32_t MODE>
+__global__ __launch_bounds__(320, 1) void k_verify_quad_hs_fold(
+    uint32_t n, const uint32_t* __restrict__ pk, const uint32_t* __restrict__ sig, const uint8_t* __restrict__ msg,
+    const uint32_t* __restrict__ off, const uint32_t* __restrict__ btab, uint8_t* __restrict__ out_valid,
+    uint64_t* __restrict__ out_bitmap, uint32_t force_wide, SbFuse sb, uint32_t hs_tune, uint32_t ps_wait,
+    uint32_t* __restrict__ diag, RowSlot tags) {
+  CMTV_URGENT();
+  const uint32_t hw = threadIdx.x >> 6, t = threadIdx.x & 63;
+  const uint32_t base = blockIdx.x * 48;
+  const uint32_t tune = hs_tune >> 8;
+  const int comb_pre = hs_comb_pre(hs_tune, kHsFoldCombPre);
+  const uint32_t helper_wave = (tune & 1u) ? 3u : 0u;
+  __shared__ uint32_t prep[48][SIG_PREP_WORDS + 1];
+  __shared__ uint2 tab_lds[3][kHsTabU2];
+  __shared__ uint2 xbuf[2 * kHsSlotU2];  // sign-bytes | P_s, then the 2-slot ring
+  __shared__ uint32_t ps_ready;
+  static_assert(sizeof(xbuf) >= 48 * (kSbFuseMaxMsg + 4 * kHsPsWords), "P_s goes behind the sign-bytes buffer");
+  uint32_t* pspt = reinterpret_cast<uint32_t*>(xbuf) + 48 * (kSbFuseMaxMsg / 4);
+  // probe slots: 0 entry, 6 HW_ID; 1 / 2 before / after barrier 1; comb wave
+  // 3 = P_s published; helper 3 = its last sum, 7 = cycles at the window
+  // barriers; quads 4 = P_s taken, 3 = cycles at the flag, 5 = exit, 7 as the
+  // helper
+  CMTV_STAMP5(0);
+  CMTV_HWID5();
+  if (threadIdx.x == 0) ps_ready = 0u;
+  __syncthreads();  // the flag is clear before any wave can set or read it
+  if (hw == 4) {
+    if (tune & 2u) __builtin_amdgcn_s_setprio(0);
+    if (tune & 4u) __builtin_amdgcn_s_setprio(3);
+    if (ps_wait != 0) {
+      const uint32_t slot = t < 48 ? t : 47;
+      const uint32_t s = base + slot;
+      const uint32_t i = s < n ? s : n - 1;
+      uint32_t sw[8];
+      load_words(sw, sig + 16 * (size_t)i + 8, 2);
+      const DevBTab bt{btab};
+      BComb16Ahead bc;
+      bc.init(sw, bt);
+#pragma unroll 1
+      for (int k = 0; k < comb_pre; k++) bc.step(bt);
+      if (t < 48) {
+#pragma unroll
+        for (int j = 0; j < 10; j++) {
+          pspt[t * kHsPsWords + j] = bc.P.X.v[j];
+          pspt[t * kHsPsWords + 10 + j] = bc.P.Y.v[j];
+          pspt[t * kHsPsWords + 20 + j] = bc.P.Z.v[j];
+        }
+      }
+      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+      if (t == 0) __hip_atomic_store(&ps_ready, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    }
+    CMTV_STAMP5(3);
+    CMTV_STAMP5(1);
+    __syncthreads();  // 1
+    CMTV_STAMP5(2);
+    const int W = (int)__builtin_amdgcn_readfirstlane((prep[0][24] >> 16) & 0xFFu);
+#pragma unroll 1
+    for (int win = W - 2; win >= 0; win--) __syncthreads();  // window win
+    return;
+  }
+  if (hw == helper_wave) {
+    const uint32_t slot = t < 48 ? t : 47;
+    const uint32_t s = base + slot;
+    const uint32_t i = s < n ? s : n - 1;
+    const uint8_t* mp;
+    uint32_t ml;
+    helper_message(sb, i, msg, off, reinterpret_cast<uint32_t*>(xbuf) + slot * (kSbFuseMaxMsg / 4), mp, ml);
+    SigPrep p;
+    q_prepare<MODE>(p, pk + 8 * (size_t)i, sig + 16 * (size_t)i, mp, ml, force_wide != 0);
+    const int W = hs_workgroup_windows(p.flags, t);
+    p.flags |= (uint32_t)W << 16;
+    if (t < 48) sig_prep_store_pair(prep[t], p);  // u is never used, so never computed
+    CMTV_STAMP5(1);
+    __syncthreads();  // 1: the scalars; the tables are built
+    CMTV_STAMP5(2);
+    uint64_t hwait = 0;  // probe build: cycles the helper waits at the window barriers
+    hs_helper_sums(p, W, &tab_lds[0][0], xbuf, t, [] { return (uint64_t)CMTV_CLOCK(); }, hwait);
+    CMTV_STAMP5_VAL(7, hwait);
+    CMTV_STAMP5(3);
+    return;
+  }
+  const uint32_t wave = hw - (hw > helper_wave ? 1u : 0u);  // the quad wave's index, 0..2
+  const uint32_t ls = wave * 16 + (t >> 2);
+  const uint32_t s = base + ls;
+  const bool active = s < n;
+  const uint32_t i = active ? s : n - 1;
+  DevQuad q;
+  DevATabQ ta{tab_lds[wave], t}, tr{tab_lds[wave] + 9 * 5 * 64, t};
+  uint64_t qwait = 0;  // probe build: cycles this quad wave waits at the window barriers
+  (void)qwait;
+  bool v = q_verify_hs_fold<MODE>(
+      q, pk + 8 * (size_t)i, sig + 16 * (size_t)i, DevBTabQ{btab}, 16 - comb_pre, ta, tr,
+      [&](fe& ps) {
+        // the comb wave's flag, polled at most ps_wait times (a wave never
+        // spins forever)
+        const uint64_t c0 = CMTV_CLOCK();
+        (void)c0;
+        bool ready = false;
+        for (uint32_t spins = 0; spins < ps_wait; spins++) {
+          ready = __hip_atomic_load(&ps_ready, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) != 0u;
+          if (ready) break;
+          __builtin_amdgcn_s_sleep(2);
+        }
+        CMTV_STAMP5_VAL(3, CMTV_CLOCK() - c0);
+        if (__builtin_expect(__ballot(ready) != __ballot(1), 0)) {
+          // the comb wave's share did not arrive in time: the quad adds those
+          // comb rows too, so the wait bounds only the time, never the verdict
+          if (t == 0 && diag) atomicAdd(diag + kDiagLatePs, 1u);
+          return false;
+        }
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+        const int lane = (int)(t & 3);
+        const uint32_t* pp = pspt + ls * kHsPsWords;
+        fe a, b;
+#pragma unroll
+        for (int j = 0; j < 10; j++) {
+          a.v[j] = pp[10 * q_p2_factor_a(lane) + j];
+          b.v[j] = pp[10 * q_p2_factor_b(lane) + j];
+        }
+        fe_mul(ps, a, b);
+        CMTV_STAMP5(4);
+        return true;
+      },
+      [&](SigPrep& p) {
+        CMTV_STAMP5(1);
+        __syncthreads();
+        CMTV_STAMP5(2);
+        sig_prep_load_pair(p, prep[ls]);
+      },
+      [&](int win, fe& c) {
+        const uint64_t c0 = CMTV_CLOCK();
+        __syncthreads();
+        qwait += CMTV_CLOCK() - c0;
+        hs_slot_load(xbuf + (win & 1) * kHsSlotU2, wave, t, c);
+      });
+  CMTV_STAMP5(5);
+  CMTV_STAMP5_VAL(7, qwait);
   quad_verdict_store(v, active, s, n, wave, t, out_valid, out_bitmap, tags);
 }
 
@@ -457,7 +632,8 @@ __global__ __launch_bounds__(256, 1) void k_verify_row4_split(
 
 hipError_t launch_verify(uint32_t mode, uint32_t n, const void* pk, const void* sig, const void* msg,
                          const void* off, const uint32_t* btab, uint32_t* atab, void* valid, void* bitmap,
-                         uint32_t kflags, hipStream_t s, const SbFuse* sb, const RowSlot* row_slot) {
+                         uint32_t kflags, hipStream_t s, const SbFuse* sb, const RowSlot* row_slot, uint32_t ps_wait,
+                         uint32_t* diag) {
   const SbFuse fz = sb ? *sb : SbFuse{};
   const uint32_t form = kflags & kFormMask;
   const uint32_t fw = (kflags & kLaunchForceWide) ? 1u : 0u;
@@ -492,8 +668,12 @@ hipError_t launch_verify(uint32_t mode, uint32_t n, const void* pk, const void* 
         // 48 signatures per 256-lane block; enough blocks for every 16-bit
         // slice of every bitmap word; of rs, its tagged entries only
         const uint32_t slices = 4 * ((n + 63) / 64);
-        hipLaunchKernelGGL(k_verify_quad_hs<M>, dim3((slices + 2) / 3), dim3(256), 0, s, n, pkp, sgp, mp, op, btab, vp,
-                           bp, fw, fz, kflags >> 16, rs);
+        if (kflags & kLaunchHsFold)
+          hipLaunchKernelGGL(k_verify_quad_hs_fold<M>, dim3((slices + 2) / 3), dim3(320), 0, s, n, pkp, sgp, mp, op,
+                             btab, vp, bp, fw, fz, kflags >> 16, ps_wait, diag, rs);
+        else
+          hipLaunchKernelGGL(k_verify_quad_hs<M>, dim3((slices + 2) / 3), dim3(256), 0, s, n, pkp, sgp, mp, op, btab,
+                             vp, bp, fw, fz, kflags >> 16, rs);
         break;
       }
       default:

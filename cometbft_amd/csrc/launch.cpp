@@ -117,7 +117,7 @@ int enqueue_verify(cmtv_ctx* ctx, CmtvDev& D, size_t n, const uint8_t* d_pk, con
   const bool lane = form == kFormLane;
   const bool row = form == kFormRow || form == kFormRow4;
   const uint32_t kflags = form | (form == kFormQuad ? ctx->hs_tune << 16 : 0u) |
-                          (ctx->force_wide ? kLaunchForceWide : 0u);
+                          (ctx->force_wide ? kLaunchForceWide : 0u) | (ctx->hs_fold ? kLaunchHsFold : 0u);
   hipError_t e = hipSuccess;
   if (lane) {
     const size_t lanes = std::min<size_t>(n, ctx->lane_chunk);
@@ -148,7 +148,8 @@ int enqueue_verify(cmtv_ctx* ctx, CmtvDev& D, size_t n, const uint8_t* d_pk, con
     else
       e = launch_verify(mode, cn, d_pk + 32 * c, d_sig + 64 * c, d_msg, d_off + c, D.d_btab,
                         static_cast<uint32_t*>(S.buf.p), d_valid ? d_valid + c : nullptr,
-                        d_bitmap ? d_bitmap + c / 64 : nullptr, kflags, s, sb, row || qtag ? &slot : nullptr);
+                        d_bitmap ? d_bitmap + c / 64 : nullptr, kflags, s, sb, row || qtag ? &slot : nullptr,
+                        ctx->ps_wait, D.d_diag);
     if (e == hipSuccess && row) e = row_slot_release(ctx, D, s, slot_k);
     if ((e = L.launched(e)) != hipSuccess) return hip_fail(e);
   }

@@ -42,8 +42,9 @@
 #define CMTV_STAMP_RT(k) CMTV_PHASE_PUT(4, 4096, k, __builtin_amdgcn_s_memrealtime())
 // a value of the wave's own (cycles summed over a loop's barriers)
 #define CMTV_STAMP_VAL(k, val) CMTV_PHASE_PUT(4, 4096, k, val)
-// five-wave workgroups (k_verify_keyed_quad_split)
+// five-wave workgroups (k_verify_keyed_quad_split, k_verify_quad_hs_fold)
 #define CMTV_STAMP5(k) CMTV_PHASE_PUT(5, 3200, k, CMTV_CLOCK())
+#define CMTV_STAMP5_VAL(k, val) CMTV_PHASE_PUT(5, 3200, k, val)
 // slot 6 of a five-wave workgroup's wave: its HW_ID (bits 5:4 the SIMD, 11:8 the CU)
 #define CMTV_HWID5()                                                                                       \
   do {                                                                                                     \
@@ -57,6 +58,7 @@
 #define CMTV_STAMP_RT(k) ((void)0)
 #define CMTV_STAMP_VAL(k, val) ((void)0)
 #define CMTV_STAMP5(k) ((void)0)
+#define CMTV_STAMP5_VAL(k, val) ((void)0)
 #define CMTV_HWID5() ((void)0)
 #define CMTV_CLOCK() 0ull
 #endif

@@ -422,6 +422,25 @@ CMTV_HD void sig_prep_load(SigPrep& p, const uint32_t* d) {
   }
   p.flags = d[24];
 }
+// the same without u (the folded form has no fixed-base scalar: a helper that
+// stores only this never computes u = k2 s mod L)
+CMTV_HD void sig_prep_store_pair(uint32_t* d, const SigPrep& p) {
+#pragma unroll
+  for (int j = 0; j < 8; j++) {
+    d[j] = p.k1[j];
+    d[8 + j] = p.k2[j];
+  }
+  d[24] = p.flags;
+}
+CMTV_HD void sig_prep_load_pair(SigPrep& p, const uint32_t* d) {
+#pragma unroll
+  for (int j = 0; j < 8; j++) {
+    p.k1[j] = d[j];
+    p.k2[j] = d[8 + j];
+    p.u[j] = 0;
+  }
+  p.flags = d[24];
+}
 
 // [u]B by the 16-position radix-2^16 comb (verify_core.h BC16 blocks): 16
 // mixed additions and no doublings, one lane per signature -- the helper
@@ -461,6 +480,49 @@ struct BComb16 {
     ge_add_table<false>(t, P, btab, BC16_BASE + j * BT16_ENTRIES + (ib > 0 ? ib - 1 : 0), d < 0, ib == 0);
     efgh_to_p3(P, t);
     j--;
+  }
+};
+
+// BComb16 with each position's row fetched one addition ahead: the row's
+// address needs only the scalar, so its load runs under the addition before
+// it instead of in front of its own (a wave of its own with nothing else to
+// hide a table miss behind: k_verify_quad_hs_fold's comb wave)
+struct BComb16Ahead {
+  struct Row {  // one niels row held in registers, as a ge_add_table source
+    fe c[3];
+    CMTV_HD void load_fe(int, int k, fe& r) const { fe_select(r, c[0], c[1], k == 1); fe_select(r, r, c[2], k == 2); }
+  };
+  ge_p3 P;
+  uint32_t lo[8], hi[8];
+  int j;
+  Row next;
+  bool neg, ident;
+  template <class BTab>
+  CMTV_HD void fetch(const BTab& btab) {
+    const int d = (int)(j >= 8 ? sc_shift_out(hi, 16) : sc_shift_out(lo, 16)) - 0x8000;
+    const int ib = d < 0 ? -d : d;
+    const int e = BC16_BASE + j * BT16_ENTRIES + (ib > 0 ? ib - 1 : 0);
+    neg = d < 0;
+    ident = ib == 0;
+#pragma unroll
+    for (int k = 0; k < 3; k++) btab.load_fe(e, k, next.c[k]);
+  }
+  template <class BTab>
+  CMTV_HD void init(const uint32_t u[8], const BTab& btab) {
+    hs_digits65536(lo, hi, u);
+    p3_identity(P);
+    j = 15;
+    fetch(btab);
+  }
+  template <class BTab>
+  CMTV_HD void step(const BTab& btab) {
+    const Row cur = next;
+    const bool c_neg = neg, c_ident = ident;
+    j--;
+    if (j >= 0) fetch(btab);
+    ge_efgh t;
+    ge_add_table<false>(t, P, cur, 0, c_neg, c_ident);
+    efgh_to_p3(P, t);
   }
 };
 
@@ -856,47 +918,46 @@ CMTV_HD void q_hs_straus(const Q& q, fe& v, fe& rc, const BTab& btab, ATab& tabA
   q_add(q, v, c);
 }
 
-// The Ed25519 helper-summed verifier (k_verify_quad_hs): decode as
-// q_verify_split, q_hs_straus, the mode's final check
-template <uint32_t MODE, class Q, class BTab, class ATab, class GetPrep, class GetS, class GetB>
-CMTV_HD bool q_verify_hs(const Q& q, const uint32_t* pk_ptr, const uint32_t* sig_ptr, const BTab& btab, ATab& tabA,
-                         ATab& tabR, int j0, const GetPrep& get_prep, const GetS& get_s, const GetB& get_b) {
+// The decode of the helper-summed verifiers: A on even lanes, R on odd ones
+// (as q_verify_split), then v = this lane's coordinate of -A, rc = of -R
+// (both extended, Z = 1)
+template <class Q>
+CMTV_HD void q_hs_decode(const Q& q, const uint32_t* pk_ptr, const uint32_t* sig_ptr, fe& v, fe& rc, bool& a_ok,
+                         bool& r_ok, bool& r_canon) {
   const int lane = q.lane();
   uint32_t w[8];
   const uint32_t* src = (lane & 1) ? sig_ptr : pk_ptr;
 #pragma unroll
   for (int i = 0; i < 8; i++) w[i] = src[i];
-  fe v, rc;
-  bool a_ok, r_ok, r_canon;
-  {
-    ge_p3 P;
-    const bool dec = p3_frombytes(P, w);
-    const bool canon = y_is_canonical(w) && !(fe_iszero(P.X) && (w[7] >> 31));
-    fe x, y, t, one;
-    fe_1(one);
-    q.template perm<QP_B0>(x, P.X);
-    q.template perm<QP_B0>(y, P.Y);
-    q.template perm<QP_B0>(t, P.T);
-    fe_pick(v, lane, x, y, one, t);  // A
-    q.template perm<QP_B1>(x, P.X);
-    q.template perm<QP_B1>(y, P.Y);
-    q.template perm<QP_B1>(t, P.T);
-    fe_pick(rc, lane, x, y, one, t);  // R
-    a_ok = q.template perm32<QP_B0>(dec ? 1u : 0u) != 0;
-    r_ok = q.template perm32<QP_B1>(dec ? 1u : 0u) != 0;
-    r_canon = q.template perm32<QP_B1>(canon ? 1u : 0u) != 0;
-    // -A and -R: negate X (lane 0) and T (lane 3)
-    const bool xt = lane == 0 || lane == 3;
-    fe_neg(t, v);
-    fe_carry(t);
-    fe_select(v, v, t, xt);
-    fe_neg(t, rc);
-    fe_carry(t);
-    fe_select(rc, rc, t, xt);
-  }
-  SigPrep p;
-  q_hs_straus(q, v, rc, btab, tabA, tabR, j0, p, get_prep, get_s, get_b);
-  const bool s_ok = (p.flags & 4u) != 0;
+  ge_p3 P;
+  const bool dec = p3_frombytes(P, w);
+  const bool canon = y_is_canonical(w) && !(fe_iszero(P.X) && (w[7] >> 31));
+  fe x, y, t, one;
+  fe_1(one);
+  q.template perm<QP_B0>(x, P.X);
+  q.template perm<QP_B0>(y, P.Y);
+  q.template perm<QP_B0>(t, P.T);
+  fe_pick(v, lane, x, y, one, t);  // A
+  q.template perm<QP_B1>(x, P.X);
+  q.template perm<QP_B1>(y, P.Y);
+  q.template perm<QP_B1>(t, P.T);
+  fe_pick(rc, lane, x, y, one, t);  // R
+  a_ok = q.template perm32<QP_B0>(dec ? 1u : 0u) != 0;
+  r_ok = q.template perm32<QP_B1>(dec ? 1u : 0u) != 0;
+  r_canon = q.template perm32<QP_B1>(canon ? 1u : 0u) != 0;
+  // -A and -R: negate X (lane 0) and T (lane 3)
+  const bool xt = lane == 0 || lane == 3;
+  fe_neg(t, v);
+  fe_carry(t);
+  fe_select(v, v, t, xt);
+  fe_neg(t, rc);
+  fe_carry(t);
+  fe_select(rc, rc, t, xt);
+}
+
+// The mode's final check of v = this lane's coordinate of X = [k2](R' - R)
+template <uint32_t MODE, class Q>
+CMTV_HD bool q_hs_final(const Q& q, const fe& v, bool s_ok, bool a_ok, bool r_ok, bool r_canon) {
   if (MODE == MODE_ZIP215) {
     const bool so = q_small_order(q, v);
     return s_ok && a_ok && r_ok && so;
@@ -908,6 +969,147 @@ CMTV_HD bool q_verify_hs(const Q& q, const uint32_t* pk_ptr, const uint32_t* sig
   const bool e0 = q.template perm32<QP_B0>(x0 ? 1u : 0u) != 0;
   const bool e1 = q.template perm32<QP_B1>(yz ? 1u : 0u) != 0;
   return s_ok && a_ok && r_ok && r_canon && e0 && e1;
+}
+
+// The Ed25519 helper-summed verifier (k_verify_quad_hs): q_hs_decode,
+// q_hs_straus, the mode's final check
+template <uint32_t MODE, class Q, class BTab, class ATab, class GetPrep, class GetS, class GetB>
+CMTV_HD bool q_verify_hs(const Q& q, const uint32_t* pk_ptr, const uint32_t* sig_ptr, const BTab& btab, ATab& tabA,
+                         ATab& tabR, int j0, const GetPrep& get_prep, const GetS& get_s, const GetB& get_b) {
+  fe v, rc;
+  bool a_ok, r_ok, r_canon;
+  q_hs_decode(q, pk_ptr, sig_ptr, v, rc, a_ok, r_ok, r_canon);
+  SigPrep p;
+  q_hs_straus(q, v, rc, btab, tabA, tabR, j0, p, get_prep, get_s, get_b);
+  return q_hs_final<MODE>(q, v, (p.flags & 4u) != 0, a_ok, r_ok, r_canon);
+}
+
+// ---- [s]B folded into R (kernels.hip k_verify_quad_hs_fold) ---------------
+//
+// B has order L and k1 = k2 k (mod 8L), so with P_s = [s]B
+//   X = [k2](R' - R) = [k2 s mod L]B - [k1]A - [k2]R = [k1](-A) + [k2](P_s - R):
+// the fixed-base term is no term of the double-scalar product at all. P_s
+// needs only the signature's s (no hash, no half-size pair), so a wave of its
+// own adds the comb's top positions from the first cycle (BComb16 on s) and
+// the quads the rest before they wait for anything; -R + P_s is formed once,
+// before R's table, and the windows are 4 doublings and the one helper-summed
+// addition: no comb digits, no u = k2 s mod L, no [u]B hand-over. R's digits
+// are flipped for a negative k2 exactly as before.
+
+// The two factors of this lane's coordinate of the projective point (X, Y, Z)
+// as an extended point: (XZ, YZ, Z^2, XY) is the same point with T Z = X Y.
+// Indices into (X, Y, Z).
+CMTV_HD int q_p2_factor_a(int lane) { return lane == 3 ? 0 : lane; }
+CMTV_HD int q_p2_factor_b(int lane) { return lane == 3 ? 1 : 2; }
+
+// v += positions j_hi-1 .. j_lo of [s]B's 16-position comb, on the quad itself
+// (v: one extended coordinate per lane): q_bcomb16's additions over the same
+// comb rows, each row fetched while the addition before it runs. Any 256-bit
+// s stays inside the comb's blocks (a digit's magnitude is at most 2^15); all
+// 16 positions sum to [s]B for s < 2^255 - 2^240 (the top field of
+// s + 0x8000...8000 does not wrap), which covers every s the s check accepts
+// (s < L).
+template <class Q, class BTab>
+CMTV_HD void q_sbase16_add(const Q& q, fe& v, const uint32_t s[8], const BTab& btab, int j_hi, int j_lo) {
+  const int lane = q.lane();
+  uint32_t lo[8], hi[8];
+  hs_digits65536(lo, hi, s);
+#pragma unroll 1
+  for (int j = 15; j >= j_hi; j--) sc_shift_out(j >= 8 ? hi : lo, 16);
+  fe cn;
+  bool neg = false, ident = false;
+  auto fetch = [&](int j) {
+    const int d = (int)(j >= 8 ? sc_shift_out(hi, 16) : sc_shift_out(lo, 16)) - 0x8000;
+    const int ib = d < 0 ? -d : d;
+    const int row = BC16_BASE + j * BT16_ENTRIES + (ib > 0 ? ib - 1 : 0);
+    neg = d < 0;
+    ident = ib == 0;
+    q_niels_load(
+        q, cn, [&](int off, fe& r) { btab.load_coord(row, off, r); }, BTAB_COORD_WORDS, 2 * BTAB_COORD_WORDS, neg);
+  };
+  if (j_hi > j_lo) fetch(j_hi - 1);
+#pragma unroll 1
+  for (int j = j_hi - 1; j >= j_lo; j--) {
+    fe c = cn;
+    const bool c_neg = neg, c_ident = ident;
+    if (j > j_lo) fetch(j - 1);
+    q_niels_fix(c, lane, c_neg, c_ident);
+    q_add(q, v, c);
+  }
+}
+
+// The quad side of the folded form after the decode (v: this lane's
+// coordinate of -A, rc: of -R, extended, Z = 1; s: the signature's s): A's
+// table; rc += positions j0-1..0 of [s]B (the quads' share of the comb, which
+// waits for nobody); get_ps(ps): this lane's coordinate of the comb wave's
+// share, positions 15..j0, extended -- false: it is not to be had, and the
+// quad adds those rows too; then the table of rc = P_s - R (Z is no longer
+// 1), get_prep, the top window and W - 1 windows of 4 doublings and
+// get_s(win, c), as q_hs_straus without its B digits.
+// Out: v = this lane's coordinate of X = [k2](R' - R), p.
+template <class Q, class BTab, class ATab, class GetPs, class GetPrep, class GetS>
+CMTV_HD void q_hs_straus_fold(const Q& q, fe& v, fe& rc, const uint32_t s[8], const BTab& btab, int j0, ATab& tabA,
+                              ATab& tabR, SigPrep& p, const GetPs& get_ps, const GetPrep& get_prep,
+                              const GetS& get_s) {
+  const int lane = q.lane();
+  q_build_table_p3(q, tabA, v);
+  q_sbase16_add(q, rc, s, btab, j0, 0);
+  fe c;
+  {
+    fe ps;
+    if (get_ps(ps)) {
+      q_to_cached(q, c, ps);
+      q_add(q, rc, c);
+    } else {
+      q_sbase16_add(q, rc, s, btab, 16, j0);
+    }
+  }
+  q_build_table_p3(q, tabR, rc);
+  get_prep(p);
+  const bool r_flip = (p.flags & 1u) != 0;
+  const int W = (p.flags >> 16) & 0xFFu ? (int)((p.flags >> 16) & 0xFFu) : q_wave_windows(q, p.flags);
+  uint32_t tA[8], tR[8];
+  hs_digits16(tA, p.k1, W);
+  hs_digits16(tR, p.k2, W);
+  {
+    // the top window, as q_hs_straus
+    const int dA = (int)sc_shift_out(tA, 4) - 8;
+    const int dR = (int)sc_shift_out(tR, 4) - 8;
+    tabA.load(dA < 0 ? -dA : dA, v);
+    fe t, r;
+    fe_neg(t, v);
+    fe_carry(t);
+    fe_select(v, v, t, dA < 0 && (lane == 0 || lane == 3));
+    tabR.load(dR < 0 ? -dR : dR, r);
+    fe_neg(t, r);
+    fe_carry(t);
+    fe_select(r, r, t, ((dR < 0) != r_flip) && (lane == 0 || lane == 3));
+    q_to_cached(q, c, r);
+    q_add(q, v, c);
+  }
+#pragma unroll 1
+  for (int win = W - 2; win >= 0; win--) {
+#pragma unroll 1
+    for (int d = 0; d < 4; d++) q_dbl(q, v);
+    get_s(win, c);
+    q_add(q, v, c);
+  }
+}
+
+// The Ed25519 folded verifier (k_verify_quad_hs_fold)
+template <uint32_t MODE, class Q, class BTab, class ATab, class GetPs, class GetPrep, class GetS>
+CMTV_HD bool q_verify_hs_fold(const Q& q, const uint32_t* pk_ptr, const uint32_t* sig_ptr, const BTab& btab, int j0,
+                              ATab& tabA, ATab& tabR, const GetPs& get_ps, const GetPrep& get_prep,
+                              const GetS& get_s) {
+  fe v, rc;
+  bool a_ok, r_ok, r_canon;
+  q_hs_decode(q, pk_ptr, sig_ptr, v, rc, a_ok, r_ok, r_canon);
+  uint32_t s[8];
+#pragma unroll
+  for (int i = 0; i < 8; i++) s[i] = sig_ptr[8 + i];
+  SigPrep p;
+  q_hs_straus_fold(q, v, rc, s, btab, j0, tabA, tabR, p, get_ps, get_prep, get_s);
+  return q_hs_final<MODE>(q, v, (p.flags & 4u) != 0, a_ok, r_ok, r_canon);
 }
 
 // One wave does everything (k_verify_quad; the host checks)

@@ -259,6 +259,13 @@ static void read_env(cmtv_ctx* ctx) {
   env_not("CMTV_EARLY_SIGS", '0', ctx->early_sigs);
   if (const char* hp = std::getenv("CMTV_HOST_POLL")) ctx->host_poll = std::atoi(hp) != 0;
   if (const char* kl = std::getenv("CMTV_FORCE_K_LATE")) ctx->keyed_wait = kl[0] == '1' ? 0u : kKeyedWaitDefault;
+  env_not("CMTV_HS_FOLD", '0', ctx->hs_fold);
+  if (const char* pl = std::getenv("CMTV_FORCE_PS_LATE")) ctx->ps_wait = pl[0] == '1' ? 0u : kPsWaitDefault;
+  {
+    uint32_t ft = 0;
+    env_int("CMTV_HS_FOLD_TUNE", 0, 7, ft);
+    ctx->hs_tune |= ft << 8;
+  }
   env_int("CMTV_KEYED_BATCH_MIN_WAVES", 1, 1l << 20, ctx->keyed_batch_min_waves);
   env_int("CMTV_KEYED_BATCH_MIN_WAVES", 1, 1l << 20, ctx->secp_batch_min_waves);
   if (std::getenv("CMTV_KEYED_BATCH_MIN_WAVES")) ctx->secp_batch_max_kb = 8;
@@ -527,14 +534,18 @@ int cmtv_sync(cmtv_ctx* ctx) {
 
 // the kernels' diagnostic counters of every usable device, summed
 static void read_diag(cmtv_ctx* ctx) {
-  uint64_t late = 0;
+  uint64_t late = 0, late_ps = 0;
   for (auto& D : ctx->devs) {
     if (D.failed || !D.d_diag) continue;
     (void)hipSetDevice(D.ordinal);
     uint32_t w[kDiagWords] = {};
-    if (hipMemcpy(w, D.d_diag, sizeof(w), hipMemcpyDeviceToHost) == hipSuccess) late += w[kDiagLateK];
+    if (hipMemcpy(w, D.d_diag, sizeof(w), hipMemcpyDeviceToHost) == hipSuccess) {
+      late += w[kDiagLateK];
+      late_ps += w[kDiagLatePs];
+    }
   }
   ctx->stats.late_k_waves = late;
+  ctx->stats.late_ps_waves = late_ps;
 }
 
 int cmtv_stats_get(cmtv_ctx* ctx, cmtv_stats* out) {

@@ -418,7 +418,14 @@ struct cmtv_ctx {
   cmtv_stats stats{};
   // CMTV_FORM: a form forced at every size it can take (kNoForm: the bands)
   uint32_t force_form = cmtv::kNoForm, force_keyed = cmtv::kNoForm;
-  uint32_t hs_tune = 0;  // CMTV_HS_PRE + 1 (bits 0..7); 0: the kernel's default
+  // CMTV_HS_PRE + 1 (bits 0..7; 0: the kernel's default), CMTV_HS_FOLD_TUNE (bits 8..10)
+  uint32_t hs_tune = 0;
+  // the Ed25519 quad form folds [s]B into R on a fifth wave
+  // (k_verify_quad_hs_fold; CMTV_HS_FOLD=0: k_verify_quad_hs), and its quads'
+  // polls for that wave's [s]B before they add the comb rows themselves
+  // (CMTV_FORCE_PS_LATE=1: 0, every quad wave does)
+  bool hs_fold = true;
+  uint32_t ps_wait = cmtv::kPsWaitDefault;
   size_t lane_chunk = cmtv::kChunk;         // signatures per lane-kernel launch (env CMTV_LANE_CHUNK)
   size_t shard_min = cmtv::kShardMinDefault;
   int sr_nops = 0;

@@ -122,6 +122,10 @@ typedef struct cmtv_stats {
   uint64_t isolated_calls;   /* latency calls (a single commit, a small
                               cmtv_verify_commits) run on the CUs those
                               masked chunks leave free (CMTV_LAT_ISOLATE) */
+  uint64_t late_ps_waves;    /* quad waves of the Ed25519 quad kernel that
+                              stopped waiting for the comb wave's [s]B and
+                              added the comb rows themselves (timing only,
+                              never a verdict)                            */
 } cmtv_stats;
 
 /* One device's share of the context's work (cmtv_device_stats_get). */
@@ -158,7 +162,11 @@ typedef struct cmtv_device_stats {
  * synchronisation in a host batch reports a HIP error, i.e. a fault found
  * after the launch; same retirement), CMTV_FORCE_K_LATE=1 (test knob: the
  * keyed split kernel's quads never wait for the hash helper and hash their
- * signatures themselves), CMTV_RCCL_LIB=path (the RCCL library to dlopen
+ * signatures themselves), CMTV_FORCE_PS_LATE=1 (test knob: the Ed25519 quad
+ * kernel's quads never wait for the comb wave's [s]B and add the comb rows
+ * themselves), CMTV_HS_FOLD=0 (the Ed25519 quad kernel keeps [u]B as a term of
+ * its windows: k_verify_quad_hs instead of k_verify_quad_hs_fold),
+ * CMTV_RCCL_LIB=path (the RCCL library to dlopen
  * instead of the system librccl; with CMTV_FORCE_RCCL a repeated ordinal then
  * gets a multi-rank communicator: the one-GPU rehearsal of the RCCL path with
  * tests/host/librccl_stub.so), CMTV_ROW_FENCE=0 (test knob: no fence on the

@@ -4,6 +4,8 @@
   make -C cometbft_amd/csrc OUT=../../abtest/libprobe.so BUILD=../../build/probe KFLAGS=-DCMTV_PHASE_PROBE
   CMTV_LIBRARY=$PWD/abtest/libprobe.so python tools/phase_probe.py [n]
   CMTV_LIBRARY=$PWD/abtest/libprobe.so python tools/phase_probe.py --sr [n]   (k_verify_sr25519_quad_hs)
+  CMTV_LIBRARY=$PWD/abtest/libprobe.so python tools/phase_probe.py --fold [n] (k_verify_quad_hs_fold, the
+      Ed25519 default; without --fold run with CMTV_HS_FOLD=0 for k_verify_quad_hs)
   (inputs resident in HBM as in bench.py; --host: host arrays through the staging / zero-copy path)
 
 Lane 0 of every wave records the shader clock at kernel entry (0), before /
@@ -14,6 +16,13 @@ per-window barriers. Printed per mode:
 the spread of workgroup starts, and for the workgroup that ends last and the
 median workgroup, when the helper and the quad waves reach each barrier --
 which of them waits, and for how long.
+
+--fold: the five-wave folded kernel's stamps (kernels.hip): per wave 0 entry,
+6 HW_ID, 1 / 2 before / after barrier 1; the comb wave (4) 3 = its share of
+[s]B published; the hash helper 3 = its last sum, 7 = cycles at the window
+barriers; the quads 3 = cycles at the flag, 4 = P_s taken, 5 = exit, 7 as
+the helper. Printed: barrier 1 per role, the comb wave's finish, the quads'
+wait at the flag, the loop length, and which wave shares the comb wave's SIMD.
 """
 import ctypes
 import json
@@ -28,10 +37,40 @@ sys.path.insert(0, ROOT)
 SLOTS = 8
 
 
+def fold_report(st, helper_wave):
+    """st: [workgroups, 5 waves, SLOTS] of k_verify_quad_hs_fold's stamps."""
+    quads = [w for w in range(4) if w != helper_wave]
+    simd = (st[:, :, 6] >> 4) & 3
+    cu = (st[:, :, 6] >> 8) & 15
+    shares = [int(((simd[:, w] == simd[:, 4]) & (cu[:, w] == cu[:, 4])).sum()) for w in range(4)]
+    flag_wait, win_wait = st[:, :, 3].copy(), st[:, :, 7].copy()
+    t0 = st[:, :, 0].min(axis=1)
+    st = st - t0[:, None, None]
+    q, h, c = st[:, quads, :], st[:, helper_wave, :], st[:, 4, :]
+    end = q[:, :, 5].max(axis=1)
+    rel = q[:, :, 2].max(axis=1)
+    med = int(np.argsort(end)[len(end) // 2])
+    return {
+        "end_median": int(np.median(end)), "end_max": int(end.max()),
+        "helper_b1_median": float(np.median(h[:, 1])), "quad_b1_median": float(np.median(q[:, :, 1])),
+        "comb_published_median": float(np.median(c[:, 3])), "comb_published_max": int(c[:, 3].max()),
+        "quad_ps_taken_median": float(np.median(q[:, :, 4])),
+        "quad_flag_wait_median": float(np.median(flag_wait[:, quads])), "quad_flag_wait_max": int(flag_wait[:, quads].max()),
+        "b1_release_median": float(np.median(rel)), "loop_median": float(np.median(end - rel)),
+        "helper_window_wait_median": float(np.median(win_wait[:, helper_wave])),
+        "quad_window_wait_median": float(np.median(win_wait[:, quads])),
+        "waves_sharing_comb_simd": {"wave%d" % w: shares[w] for w in range(4)}, "workgroups": int(st.shape[0]),
+        "median_wg": {"index": med, "helper_at_b1": int(h[med, 1]), "quads_at_b1": [int(x) for x in q[med, :, 1]],
+                      "comb_published": int(c[med, 3]), "b1_release": int(rel[med]),
+                      "quads_end": [int(x) for x in q[med, :, 5]]},
+    }
+
+
 def main():
+    fold = "--fold" in sys.argv
     sr = "--sr" in sys.argv
     host = "--host" in sys.argv  # host arrays (zero-copy / staged inputs) instead of HBM-resident ones
-    argv = [a for a in sys.argv[1:] if a not in ("--sr", "--host")]
+    argv = [a for a in sys.argv[1:] if a not in ("--sr", "--host", "--fold")]
     n = int(argv[0]) if len(argv) > 0 else 10_000
     # signatures per 4-wave workgroup: 48 (k_verify_quad_split) or 3 (the row
     # kernel, k_verify_row_split, which the library picks up to kRowMax)
@@ -84,8 +123,13 @@ def main():
                 torch.cuda.synchronize()
                 v = d_valid.cpu().numpy()
         assert v.all()
-        buf = np.zeros(wgs * 4 * SLOTS, np.uint64)
+        buf = np.zeros(wgs * (5 if fold else 4) * SLOTS, np.uint64)
         assert fn(buf.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)), buf.size) == 0
+        if fold:
+            helper_wave = 3 if int(os.environ.get("CMTV_HS_FOLD_TUNE", "0")) & 1 else 0
+            out[name] = fold_report(buf.reshape(wgs, 5, SLOTS).astype(np.int64), helper_wave)
+            print(name, json.dumps(out[name]), flush=True)
+            continue
         st = buf.reshape(wgs, 4, SLOTS).astype(np.int64)
         waits = st[:, :, 6].copy()  # k_verify_quad_hs: cycle counts, not stamps
         # each workgroup against its own first entry: s_memtime counters of
