@@ -58,6 +58,8 @@ EXPORTS = (
     "cmtv_batch_new", "cmtv_batch_add", "cmtv_batch_len", "cmtv_batch_verify", "cmtv_batch_reset",
     "cmtv_batch_free", "cmtv_verify_commit", "cmtv_verify_commit_typed", "cmtv_verify_commits", "cmtv_verify_commits_typed", "cmtv_verdict_cache", "cmtv_keyset_cache", "cmtv_vote_sign_bytes", "cmtv_pubkeys_ed25519", "cmtv_sign_ed25519",
     "cmtv_alloc_pinned", "cmtv_free_pinned",
+    "cmtv_merkle_root", "cmtv_merkle_roots", "cmtv_valset_hash", "cmtv_valset_hashes", "cmtv_commit_hash",
+    "cmtv_commit_hashes", "cmtv_validator_bytes", "cmtv_commit_sig_bytes",
 )
 
 
@@ -245,6 +247,22 @@ def lib() -> ctypes.CDLL:
     L.cmtv_alloc_pinned.restype = ctypes.c_int
     L.cmtv_free_pinned.argtypes = [vp, vp]
     L.cmtv_free_pinned.restype = ctypes.c_int
+    L.cmtv_merkle_root.argtypes = [vp, sz, _u8p, u32p, _u8p]
+    L.cmtv_merkle_root.restype = ctypes.c_int
+    L.cmtv_merkle_roots.argtypes = [vp, sz, u32p, _u8p, u32p, _u8p]
+    L.cmtv_merkle_roots.restype = ctypes.c_int
+    L.cmtv_valset_hash.argtypes = [vp, ctypes.POINTER(cmtv_valset), _u8p, _u8p]
+    L.cmtv_valset_hash.restype = ctypes.c_int
+    L.cmtv_valset_hashes.argtypes = [vp, sz, ctypes.POINTER(cmtv_valset), ctypes.POINTER(_u8p), _u8p]
+    L.cmtv_valset_hashes.restype = ctypes.c_int
+    L.cmtv_commit_hash.argtypes = [vp, ctypes.POINTER(cmtv_commit), _u8p]
+    L.cmtv_commit_hash.restype = ctypes.c_int
+    L.cmtv_commit_hashes.argtypes = [vp, sz, ctypes.POINTER(cmtv_commit), _u8p]
+    L.cmtv_commit_hashes.restype = ctypes.c_int
+    L.cmtv_validator_bytes.argtypes = [u32, _u8p, sz, i64, _u8p, sz]
+    L.cmtv_validator_bytes.restype = ctypes.c_int
+    L.cmtv_commit_sig_bytes.argtypes = [u32, _u8p, i64, i32, _u8p, sz, _u8p, sz]
+    L.cmtv_commit_sig_bytes.restype = ctypes.c_int
     _lib = L
     return L
 

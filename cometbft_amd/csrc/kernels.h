@@ -1,6 +1,6 @@
 // kernels.h -- host-side launchers for the gfx950 kernels (kernels.hip,
 // keyed_forms.hip, keyed_lane.hip, keygen.hip, sr25519.hip, secp256k1.hip,
-// signbytes.hip).
+// signbytes.hip, merkle.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -184,5 +184,28 @@ hipError_t launch_bulk_gather(uint32_t n_c, uint32_t m, const void* desc, const 
 hipError_t launch_pubkey(uint32_t n, const void* seeds, const uint32_t* btab, void* out_pk, hipStream_t s);
 hipError_t launch_sign(uint32_t n, const void* seeds, const void* key_idx, const void* msg, const void* off,
                        const uint32_t* btab, void* out_sig, hipStream_t s);
+
+// One pass of the merkle engine (merkle.hip, merkle.h): n_wg workgroups, each
+// an aligned block of one tree's leaves reduced to node g of `out` (8 words a
+// node). wg_off / leaf_off: n_trees + 1 words each. What a leaf is:
+//   kMerkleItems      item g = var[off[g] .. off[g + 1])
+//   kMerkleValidators key g = var[off[g] .. off[g + 1]), power i64[g], key
+//                     type u8[g] (u8 null: every key Ed25519)
+//   kMerkleCommitSigs flag u8[g], seconds i64[g], nanos i32[g], address
+//                     addr[20 g ..), signature var[off[g] .. off[g + 1])
+//   kMerkleNodes      node g of `nodes`, the previous pass's output
+enum MerkleLeafKind { kMerkleItems = 0, kMerkleValidators = 1, kMerkleCommitSigs = 2, kMerkleNodes = 3 };
+struct MerkleLeaves {
+  const uint8_t* var = nullptr;
+  const uint32_t* off = nullptr;
+  const int64_t* i64 = nullptr;
+  const int32_t* i32 = nullptr;
+  const uint8_t* u8 = nullptr;
+  const uint8_t* addr = nullptr;
+  const uint32_t* nodes = nullptr;
+};
+hipError_t launch_merkle_pass(MerkleLeafKind kind, const MerkleLeaves& leaves, const uint32_t* wg_off,
+                              const uint32_t* leaf_off, uint32_t n_trees, uint32_t n_wg, uint32_t* out,
+                              hipStream_t s);
 
 }  // namespace cmtv

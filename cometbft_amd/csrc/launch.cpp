@@ -54,7 +54,7 @@ static void take_tags(CmtvDev& D, RowSlot& slot, uint32_t width) {
 }
 
 // CMTV_FAULT_AT: true when this verification launch is the one to fail
-static bool fault_hit(cmtv_ctx* ctx) {
+bool fault_hit(cmtv_ctx* ctx) {
   ctx->launch_seq++;
   if (ctx->fault_at && ctx->launch_seq == ctx->fault_at) {
     ctx->stats.faults_injected++;

@@ -170,6 +170,12 @@ static void release_device(CmtvDev& D) {
   for (DevBuf* b : {&D.scratch.buf, &D.d_in, &D.d_out, &D.d_all, &D.secp_in, &D.secp_out}) b->release();
   for (HostBuf* b : {&D.h_in, &D.h_out, &D.h_zc, &D.h_tags, &D.h_zin}) b->release();
   D.d_tags = nullptr;  // h_tags' device pointer
+  for (MerkleSlot& M : D.merkle) {
+    for (DevBuf* b : {&M.d_in, &M.d_nodes}) b->release();
+    for (HostBuf* b : {&M.h_in, &M.h_out}) b->release();
+    if (M.done) (void)hipEventDestroy(M.done);
+    M.done = nullptr;
+  }
   for (uint32_t** p : {&D.d_btab, &D.d_srprog, &D.d_secp_gtab, &D.d_diag, &D.d_rowslots}) {
     if (*p) (void)hipFree(*p);
     *p = nullptr;

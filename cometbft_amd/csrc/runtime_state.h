@@ -1,7 +1,7 @@
 // runtime_state.h -- the state of a context and its devices, the constants of
 // the verification forms and the small helpers every launch path inlines.
 // Private to the runtime's own files (runtime.cpp, launch.cpp, host_batch.cpp,
-// gather.cpp, keyset.cpp, bulk_lane.cpp): the commit and pipeline layers see
+// gather.cpp, keyset.cpp, bulk_lane.cpp, merkle.cpp): the commit and pipeline layers see
 // runtime_internal.h only.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -329,6 +329,16 @@ struct BulkLane {
   Scratch scratch;
 };
 
+// A staging slot of the merkle engine (merkle.cpp): a run's pinned staging
+// block and its copy on the device, the passes' nodes, the roots back, and
+// the event after them. Two per device: one run is packed while the other
+// is hashed.
+struct MerkleSlot {
+  HostBuf h_in, h_out;
+  DevBuf d_in, d_nodes;
+  hipEvent_t done = nullptr;
+};
+
 // Per-device state of a context.
 struct CmtvDev {
   int ordinal = 0;
@@ -341,6 +351,7 @@ struct CmtvDev {
   uint32_t* d_secp_gtab = nullptr;
   DevBuf secp_in, secp_out;
   std::vector<uint8_t> secp_stage;  // verify_secp_templated_locked's staging block, kept between calls
+  MerkleSlot merkle[2];  // the merkle calls' own staging (devs[0] only)
   DevBuf d_in, d_out, d_all;
   HostBuf h_in, h_out;
   // small single-device host batches: the kernel writes the verdict bitmap
@@ -697,6 +708,9 @@ inline bool keyed_fuse_ok(const cmtv_ctx* ctx, size_t n) { return keyed_form(ctx
 // ---------------------------------------------------------------- across files
 // runtime.cpp: completed timing pairs of every usable device -> stats
 void harvest(cmtv_ctx* ctx, bool blocking);
+
+// launch.cpp: CMTV_FAULT_AT -- counts a launch, true when it is the one to fail
+bool fault_hit(cmtv_ctx* ctx);
 
 // launch.cpp: enqueue verification of n signatures whose inputs are in device
 // memory of device D (current on this thread), on stream s

@@ -142,6 +142,14 @@ class Commit:
             raise ReferencePanic(f"Unknown BlockIDFlag: {cs.block_id_flag}")
         return vote_sign_bytes(chain_id, PRECOMMIT_TYPE, self.height, self.round, bid, *cs.timestamp)
 
+    def hash(self, ctx: Context | None = None) -> bytes:
+        """Commit.Hash() (types/block.go:894) on the device (cmtv_commit_hash)."""
+        ctx = ctx or default_context()
+        cm, keep = _pack_commit(self)
+        out = (ctypes.c_uint8 * 32)()
+        N.check(N.lib().cmtv_commit_hash(ctx.handle, ctypes.byref(cm), out), "cmtv_commit_hash")
+        return bytes(out)
+
 
 def vote_sign_bytes(chain_id: str, vote_type: int, height: int, round_: int, block_id: Optional[BlockID],
                     ts_seconds: int, ts_nanos: int) -> bytes:
@@ -178,6 +186,18 @@ class Validator:
         h = hashlib.sha256(self.pub_key).digest()
         return _ripemd160.ripemd160(h) if self.key_type == "secp256k1" else h[:20]
 
+    def bytes(self) -> bytes:
+        """Validator.Bytes() (types/validator.go:117), the leaf of
+        ValidatorSet.Hash(), through the library's host encoder."""
+        if self.key_type not in N.KEY_TYPES:
+            raise ValueError(f"unknown key type {self.key_type!r}")
+        pk = (ctypes.c_uint8 * max(len(self.pub_key), 1)).from_buffer_copy(self.pub_key or b"\0")
+        buf = (ctypes.c_uint8 * 96)()
+        n = N.lib().cmtv_validator_bytes(N.KEY_TYPES[self.key_type], pk, len(self.pub_key), self.voting_power, buf, 96)
+        if n < 0:
+            raise N.CmtvError(int(n), "cmtv_validator_bytes")
+        return bytes(buf[:n])
+
 
 class ValidatorSet:
     def __init__(self, validators: Sequence[Validator]):
@@ -207,6 +227,14 @@ class ValidatorSet:
                           voting_power=vp.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), addrs=_p8(ad),
                           proposer_priority=pp.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)))
         return s, self._packed
+
+    def hash(self, ctx: Context | None = None) -> bytes:
+        """ValidatorSet.Hash() (types/validator_set.go:347) on the device (cmtv_valset_hash)."""
+        ctx = ctx or default_context()
+        vs, keep = self._pack()
+        out = (ctypes.c_uint8 * 32)()
+        N.check(N.lib().cmtv_valset_hash(ctx.handle, ctypes.byref(vs), _key_types(keep[5]), out), "cmtv_valset_hash")
+        return bytes(out)
 
     # ----------------------------------------------------------------- verify
     def verify_commit(self, chain_id: str, block_id: BlockID, height: int, commit: Commit,
@@ -266,6 +294,85 @@ def _pack_commit(commit: Commit, arena: _Arena | None = None):
                       ts_nanos=ts_n.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), sigs=_p8(sb), sig_off=_p32(so),
                       val_addrs=_p8(ad))
     return c, (flags, ts_s, ts_n, sb, so, ad, keep)
+
+
+def _key_types(kt: np.ndarray):
+    """The packed CMTV_KEY_* array of a set, or None (NULL) when every key is Ed25519."""
+    return _p8(kt) if kt[:-1].any() else None
+
+
+def _roots(buf, n: int) -> list:
+    raw = bytes(buf)
+    return [raw[32 * i: 32 * i + 32] for i in range(n)]
+
+
+def merkle_roots(trees, ctx: Context | None = None) -> list:
+    """HashFromByteSlices (crypto/merkle/tree.go:9) of every tree, a sequence
+    of sequences of byte strings, in one cmtv_merkle_roots call."""
+    ctx = ctx or default_context()
+    trees = [list(t) for t in trees]
+    if not trees:
+        return []
+    items = [it for t in trees for it in t]
+    tree_off = np.zeros(len(trees) + 1, np.uint32)
+    tree_off[1:] = np.cumsum([len(t) for t in trees])
+    item_off = np.zeros(len(items) + 1, np.uint32)
+    if items:
+        item_off[1:] = np.cumsum([len(it) for it in items])
+    blob = np.frombuffer(b"".join(items) + b"\0", np.uint8).copy()
+    out = (ctypes.c_uint8 * (32 * len(trees)))()
+    N.check(N.lib().cmtv_merkle_roots(ctx.handle, len(trees), _p32(tree_off), _p8(blob), _p32(item_off), out),
+            "cmtv_merkle_roots")
+    return _roots(out, len(trees))
+
+
+def merkle_root(items, ctx: Context | None = None) -> bytes:
+    """HashFromByteSlices of one list of byte strings (cmtv_merkle_root)."""
+    ctx = ctx or default_context()
+    items = list(items)
+    item_off = np.zeros(len(items) + 1, np.uint32)
+    if items:
+        item_off[1:] = np.cumsum([len(it) for it in items])
+    blob = np.frombuffer(b"".join(items) + b"\0", np.uint8).copy()
+    out = (ctypes.c_uint8 * 32)()
+    N.check(N.lib().cmtv_merkle_root(ctx.handle, len(items), _p8(blob), _p32(item_off), out), "cmtv_merkle_root")
+    return bytes(out)
+
+
+def valset_hashes(sets, ctx: Context | None = None) -> list:
+    """ValidatorSet.Hash() of every set in one cmtv_valset_hashes call."""
+    ctx = ctx or default_context()
+    sets = list(sets)
+    if not sets:
+        return []
+    vs_arr = (N.cmtv_valset * len(sets))()
+    kt_arr = (ctypes.POINTER(ctypes.c_uint8) * len(sets))()
+    keep = []
+    for i, s in enumerate(sets):
+        vs_arr[i], kv = s._pack()
+        kt = _key_types(kv[5])
+        if kt is not None:
+            kt_arr[i] = kt
+        keep.append(kv)
+    out = (ctypes.c_uint8 * (32 * len(sets)))()
+    N.check(N.lib().cmtv_valset_hashes(ctx.handle, len(sets), vs_arr, kt_arr, out), "cmtv_valset_hashes")
+    return _roots(out, len(sets))
+
+
+def commit_hashes(commits, ctx: Context | None = None) -> list:
+    """Commit.Hash() of every commit in one cmtv_commit_hashes call."""
+    ctx = ctx or default_context()
+    commits = list(commits)
+    if not commits:
+        return []
+    cm_arr = (N.cmtv_commit * len(commits))()
+    keep = []
+    for i, c in enumerate(commits):
+        cm_arr[i], kc = _pack_commit(c)
+        keep.append(kc)
+    out = (ctypes.c_uint8 * (32 * len(commits)))()
+    N.check(N.lib().cmtv_commit_hashes(ctx.handle, len(commits), cm_arr, out), "cmtv_commit_hashes")
+    return _roots(out, len(commits))
 
 
 def _verify(vals: ValidatorSet, kind, chain_id, block_id, height, commit, num, den, ctx, mode):

@@ -643,6 +643,70 @@ int64_t cmtv_vote_sign_bytes(const char* chain_id, size_t chain_id_len, int32_t 
                              int32_t round, const cmtv_block_id* block_id, int64_t ts_seconds, int32_t ts_nanos,
                              uint8_t* out, size_t cap);
 
+/* ------------------------------------------------------------ merkle roots */
+
+/* RFC 6962 merkle roots on the device (crypto/merkle/tree.go:9
+ * HashFromByteSlices, hash.go:14-26): an empty list hashes to SHA-256(""), a
+ * leaf to SHA-256(0x00 || item), an inner node to SHA-256(0x01 || left ||
+ * right), split at the largest power of two below n. The calls are blocking
+ * and thread-safe; they run on the context's first device (CMTV_ENODEV once
+ * it is retired) on its stream, with staging of their own. Argument errors
+ * are found before any device work, and no call writes to out unless it
+ * returns CMTV_OK. Any number of trees and bytes: a large call is cut into
+ * runs internally. Replaces: the per-block hashing of state/validation.go:73,79,
+ * light/verifier.go:183, types/light.go:37 and types/block.go:75.
+ *
+ * cmtv_merkle_root: n items concatenated in items, item i =
+ * items[item_off[i] .. item_off[i + 1]) (n + 1 offsets, not decreasing;
+ * item_off may be NULL when n is 0, items when every item is empty).
+ * cmtv_merkle_roots: n_trees trees; tree t holds items tree_off[t] ..
+ * tree_off[t + 1] (not decreasing); out n_trees x 32 bytes. */
+int cmtv_merkle_root(cmtv_ctx* ctx, size_t n, const uint8_t* items, const uint32_t* item_off, uint8_t out[32]);
+int cmtv_merkle_roots(cmtv_ctx* ctx, size_t n_trees, const uint32_t* tree_off, const uint8_t* items,
+                      const uint32_t* item_off, uint8_t* out);
+
+/* ValidatorSet.Hash() (types/validator_set.go:347): the root over
+ * Validator.Bytes() of every validator (types/validator.go:117-133,
+ * SimpleValidator proto/tendermint/types/validator.pb.go:361-384, PublicKey
+ * proto/tendermint/crypto/keys.pb.go:376-402, crypto/encoding/codec.go:20-38),
+ * the leaves encoded on the device from pubkeys, pk_off and voting_power
+ * (addrs and proposer_priority are not read). key_types as in
+ * cmtv_verify_commit_typed (NULL: every key is Ed25519). CMTV_EINVAL: an
+ * sr25519 key (the reference panics there), a type above
+ * CMTV_KEY_SR25519, a key of 0 or of more than 64 bytes (no codec yields
+ * one). cmtv_valset_hashes: n sets, key_types[i] NULL or vals[i].n_vals
+ * bytes (the array itself may be NULL), out n x 32 bytes. */
+int cmtv_valset_hash(cmtv_ctx* ctx, const cmtv_valset* vals, const uint8_t* key_types, uint8_t out[32]);
+int cmtv_valset_hashes(cmtv_ctx* ctx, size_t n, const cmtv_valset* vals, const uint8_t* const* key_types,
+                       uint8_t* out);
+
+/* Commit.Hash() (types/block.go:894): the root over
+ * CommitSig.ToProto().Marshal() of every signature
+ * (proto/tendermint/types/types.pb.go:1563-1596), the leaves encoded on the
+ * device from flags, ts_seconds, ts_nanos, sigs, sig_off and val_addrs
+ * (height, round and block_id are not read). A commit with a signature of
+ * more than 64 bytes is encoded on the host instead, with the same root.
+ * The struct-of-arrays form has a fixed 20-byte address slot per signature:
+ * an Absent signature contributes no address field, every other flag its 20
+ * bytes. This differs from the reference only for an Absent CommitSig that
+ * carries an address, which CommitSig.ValidateBasic rejects before the hash
+ * is compared. CMTV_EINVAL: val_addrs NULL with a signature that is not
+ * Absent; a timestamp outside [-62135596800, 253402300800) seconds or
+ * [0, 10^9) nanoseconds (gogo/protobuf's StdTimeMarshal fails and the
+ * reference panics; that library is not in the reference tree, the bounds
+ * are from its public source). cmtv_commit_hashes: out n x 32 bytes. */
+int cmtv_commit_hash(cmtv_ctx* ctx, const cmtv_commit* commit, uint8_t out[32]);
+int cmtv_commit_hashes(cmtv_ctx* ctx, size_t n, const cmtv_commit* commits, uint8_t* out);
+
+/* The two leaf encodings on the host (no device): Validator.Bytes() and
+ * CommitSig.ToProto().Marshal(), with the CMTV_EINVAL rules above
+ * (addr20_or_null NULL: no address field; any flag, sig_len up to 2^30).
+ * They return the length or a negative code, and write the bytes when they
+ * fit cap (as cmtv_vote_sign_bytes). */
+int cmtv_validator_bytes(uint32_t key_type, const uint8_t* pk, size_t pk_len, int64_t power, uint8_t* out, size_t cap);
+int cmtv_commit_sig_bytes(uint32_t flag, const uint8_t* addr20_or_null, int64_t ts_seconds, int32_t ts_nanos,
+                          const uint8_t* sig, size_t sig_len, uint8_t* out, size_t cap);
+
 /* ------------------------------------------------------------ test-data generation */
 
 /* RFC 8032 key generation and deterministic signing on the device (the
