@@ -187,7 +187,7 @@ struct PipeConfig {
   bool direct = true;  // CMTV_PIPE_DIRECT=0: always pack (A/B, tests)
   size_t chunk_masked = 0;  // a chunk on a CU-masked lane (latency_recent): one round of its CUs
   // a direct chunk ends where its DMA extents pass span_factor x the bytes
-  // its plans read + span_slack (pipeline.cpp cut_chunk; tests shrink them)
+  // its plans read + span_slack (pipeline.cpp SpanAcc::over, PipeRun::cut_chunk; tests shrink them)
   uint64_t span_factor = 4, span_slack = 64ull << 20;
   // bulk_prepare outside the context lock (CMTV_SPLIT_SUBMIT)
   bool split_submit = true;
