@@ -11,7 +11,9 @@
 //   fe_add     : no carry; limbs < 2^27 / 2^26 when both inputs carried
 //   fe_sub     : f + 2p - g, no carry; g must be carried; limbs < 3*2^26 / 3*2^25
 // Multiplier input bound: every limb < 2^27.7 (19*g_i must fit in 32 bits and
-// the 267*B^2 worst-case column sum must fit in 64 bits). Square input bound:
+// the 267*B^2 worst-case column sum, plus the carry that the serial chain
+// brings into it, must fit in 64 bits: column sum + incoming carry < 2^64,
+// see fe_chain below). Square input bound:
 // odd limbs < 2^26.7 (38*f_i fits 32 bits). The point formulas in ge25519.h
 // keep every operand inside these bounds (checked by tests/host/ in a bounds-
 // checking host build).
@@ -125,7 +127,87 @@ CMTV_HD void fe_select(fe& h, const fe& a, const fe& b, bool take_b) {
   for (int i = 0; i < 10; i++) h.v[i] = take_b ? b.v[i] : a.v[i];
 }
 
-#define CMTV_MUL64(a, b) ((uint64_t)(a) * (uint64_t)(b))
+// Column sums are 64-bit; a bounds-checking host build keeps them in 128 bits
+// so that "column sum plus incoming carry < 2^64" can be asserted.
+#ifdef CMTV_BOUNDS_CHECK
+typedef unsigned __int128 fe_acc_t;
+#define CMTV_ASSERT_COL(h) CMTV_ASSERT(((h) >> 64) == 0)
+#else
+typedef uint64_t fe_acc_t;
+#define CMTV_ASSERT_COL(h) ((void)0)
+#endif
+#define CMTV_MUL64(a, b) ((fe_acc_t)(uint64_t)(a) * (uint64_t)(b))
+
+// The carry chain of a product, selectable per call site:
+//   FE_CHAIN_SERIAL  columns strictly in order 0 -> 1 -> ... -> 9, column i's
+//                    carry being the addend of column i + 1's first
+//                    v_mad_u64_u32, so that the addition of a link costs no
+//                    instruction; then 19 c_9 into limb 0 and limb 0 -> 1.
+//                    A lone wave issues a dependent MAD as fast as an
+//                    independent one, so the longer chain is free there.
+//   FE_CHAIN_REF10   all ten column sums first, then fe_reduce64's two
+//                    interleaved streams (the chain up to round 7); for a
+//                    kernel in which several waves share a SIMD and the
+//                    dependency binds.
+// Column bound of the serial chain: column sum plus incoming carry < 2^64. The
+// largest column sum is 267 B^2 < 2^63.57 (B = MUL_BOUND - 1) and a carry is
+// below 2^64 / 2^25 = 2^39, so the sum stays below 2^63.58. Output limbs: 0 and
+// 2..9 are masked after their last addition (< 2^26 / 2^25); limb 1 takes
+// limb 0's second carry, (2^26 - 1 + 19 c_9) >> 26 < 2^13, on top of its mask.
+enum fe_chain : int { FE_CHAIN_SERIAL = 0, FE_CHAIN_REF10 = 1 };
+
+// The serial chain's multiply-adds: acc + a b with acc as operand C. From plain
+// C the optimiser re-associates a column's sum: it starts the MAD chain at a
+// product and adds the carry last, with a 64-bit add. A partial sum that has a
+// second use is left where it is, so fe_pin makes every partial sum an input
+// of an empty asm. The asm's output is `later`, a multiplier that the chain
+// reads two instructions on: the products then depend on the asm statements
+// (the optimiser cannot keep the one and drop the other), nothing is emitted,
+// and no instruction reads an asm's output directly (the compiler would put an
+// s_nop between the two).
+CMTV_HD void fe_pin(fe_acc_t acc, uint32_t& later) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  asm("" : "+v"(later) : "v"(acc));
+#endif
+}
+
+// the last product of a column, the last but one (pinned to nxt, which the
+// next column's first product reads: the last product and the carry's shift
+// lie between), and any earlier one (pinned to the next product but one)
+CMTV_HD fe_acc_t fe_mac_terms(fe_acc_t acc, uint32_t& nxt, uint32_t& a, uint32_t& b) {
+  return acc + CMTV_MUL64(a, b);
+}
+CMTV_HD fe_acc_t fe_mac_terms(fe_acc_t acc, uint32_t& nxt, uint32_t& a, uint32_t& b, uint32_t& a1, uint32_t& b1) {
+  acc += CMTV_MUL64(a, b);
+  fe_pin(acc, nxt);
+  return fe_mac_terms(acc, nxt, a1, b1);
+}
+template <class... T>
+CMTV_HD fe_acc_t fe_mac_terms(fe_acc_t acc, uint32_t& nxt, uint32_t& a, uint32_t& b, uint32_t& a1, uint32_t& b1,
+                              uint32_t& a2, uint32_t& b2, T&... rest) {
+  acc += CMTV_MUL64(a, b);
+  fe_pin(acc, b2);
+  return fe_mac_terms(acc, nxt, a1, b1, a2, b2, rest...);
+}
+CMTV_HD fe_acc_t fe_sum_terms(fe_acc_t acc) { return acc; }
+template <class... T>
+CMTV_HD fe_acc_t fe_sum_terms(fe_acc_t acc, uint32_t a, uint32_t b, T... rest) {
+  return fe_sum_terms(acc + CMTV_MUL64(a, b), rest...);
+}
+
+// One column: the sum of the products a b of the term list. In the serial
+// chain it starts from the carry of `prev`, the column before it (a limb of
+// `bits` bits), and every product is a MAD onto the running sum; nxt is a
+// multiplier that the chain reads first after this column (every later
+// column's first product has it, and no column's last product).
+template <fe_chain CH, class... T>
+CMTV_HD fe_acc_t fe_column(uint32_t& nxt, fe_acc_t prev, int bits, uint32_t& a, uint32_t& b, T&... rest) {
+  if constexpr (CH == FE_CHAIN_SERIAL) {
+    return fe_mac_terms((fe_acc_t)((uint64_t)prev >> bits), nxt, a, b, rest...);
+  } else {
+    return fe_sum_terms(CMTV_MUL64(a, b), rest...);
+  }
+}
 
 // carry chain on ten 64-bit column sums (ref10 interleaving shortens the
 // dependency chain: two independent carry streams 0->4 and 4->9)
@@ -149,85 +231,100 @@ CMTV_HD void fe_reduce64(fe& h, uint64_t h0, uint64_t h1, uint64_t h2, uint64_t 
   h.v[8] = (uint32_t)h8; h.v[9] = (uint32_t)h9;
 }
 
+// end of the serial chain: h1..h9 already hold their incoming carries, so a
+// limb is its column's low bits; the carry out of limb 9 wraps (x 19) into
+// limb 0, whose carry lands on the masked limb 1
+CMTV_HD void fe_wrap_serial(fe& h, uint32_t lo0, uint64_t h1, uint64_t h2, uint64_t h3, uint64_t h4,
+                            uint64_t h5, uint64_t h6, uint64_t h7, uint64_t h8, uint64_t h9) {
+  const uint64_t t = (uint64_t)(lo0 & M26) + 19 * (h9 >> 25);
+  h.v[0] = (uint32_t)t & M26;
+  h.v[1] = ((uint32_t)h1 & M25) + (uint32_t)(t >> 26);
+  h.v[2] = (uint32_t)h2 & M26; h.v[3] = (uint32_t)h3 & M25; h.v[4] = (uint32_t)h4 & M26;
+  h.v[5] = (uint32_t)h5 & M25; h.v[6] = (uint32_t)h6 & M26; h.v[7] = (uint32_t)h7 & M25;
+  h.v[8] = (uint32_t)h8 & M26; h.v[9] = (uint32_t)h9 & M25;
+#ifdef CMTV_BOUNDS_CHECK
+  for (int i = 0; i < 10; i++) CMTV_ASSERT(h.v[i] <= ((i & 1) ? M25 : M26) + (i == 1 ? (1u << 13) : 0u));
+#endif
+}
+
+template <fe_chain CH>
+CMTV_HD void fe_finish(fe& h, uint32_t lo0, fe_acc_t h0, fe_acc_t h1, fe_acc_t h2, fe_acc_t h3, fe_acc_t h4, fe_acc_t h5,
+                       fe_acc_t h6, fe_acc_t h7, fe_acc_t h8, fe_acc_t h9) {
+  CMTV_ASSERT_COL(h0); CMTV_ASSERT_COL(h1); CMTV_ASSERT_COL(h2); CMTV_ASSERT_COL(h3); CMTV_ASSERT_COL(h4);
+  CMTV_ASSERT_COL(h5); CMTV_ASSERT_COL(h6); CMTV_ASSERT_COL(h7); CMTV_ASSERT_COL(h8); CMTV_ASSERT_COL(h9);
+  if constexpr (CH == FE_CHAIN_SERIAL) {
+    fe_wrap_serial(h, lo0, (uint64_t)h1, (uint64_t)h2, (uint64_t)h3, (uint64_t)h4, (uint64_t)h5,
+                   (uint64_t)h6, (uint64_t)h7, (uint64_t)h8, (uint64_t)h9);
+  } else {
+    fe_reduce64(h, (uint64_t)h0, (uint64_t)h1, (uint64_t)h2, (uint64_t)h3, (uint64_t)h4, (uint64_t)h5,
+                (uint64_t)h6, (uint64_t)h7, (uint64_t)h8, (uint64_t)h9);
+  }
+}
+
+template <fe_chain CH = FE_CHAIN_SERIAL>
 CMTV_HD void fe_mul(fe& h, const fe& f, const fe& g) {
   CMTV_SCHED_FENCE();
 #ifdef CMTV_BOUNDS_CHECK
   for (int i = 0; i < 10; i++) CMTV_ASSERT(f.v[i] < MUL_BOUND && g.v[i] < MUL_BOUND);
 #endif
-  const uint32_t f0 = f.v[0], f1 = f.v[1], f2 = f.v[2], f3 = f.v[3], f4 = f.v[4];
-  const uint32_t f5 = f.v[5], f6 = f.v[6], f7 = f.v[7], f8 = f.v[8], f9 = f.v[9];
-  const uint32_t g0 = g.v[0], g1 = g.v[1], g2 = g.v[2], g3 = g.v[3], g4 = g.v[4];
-  const uint32_t g5 = g.v[5], g6 = g.v[6], g7 = g.v[7], g8 = g.v[8], g9 = g.v[9];
-  const uint32_t g1_19 = 19 * g1, g2_19 = 19 * g2, g3_19 = 19 * g3, g4_19 = 19 * g4, g5_19 = 19 * g5;
-  const uint32_t g6_19 = 19 * g6, g7_19 = 19 * g7, g8_19 = 19 * g8, g9_19 = 19 * g9;
-  const uint32_t f1_2 = 2 * f1, f3_2 = 2 * f3, f5_2 = 2 * f5, f7_2 = 2 * f7, f9_2 = 2 * f9;
+  uint32_t f0 = f.v[0], f1 = f.v[1], f2 = f.v[2], f3 = f.v[3], f4 = f.v[4];
+  uint32_t f5 = f.v[5], f6 = f.v[6], f7 = f.v[7], f8 = f.v[8], f9 = f.v[9];
+  uint32_t g0 = g.v[0], g1 = g.v[1], g2 = g.v[2], g3 = g.v[3], g4 = g.v[4];
+  uint32_t g5 = g.v[5], g6 = g.v[6], g7 = g.v[7], g8 = g.v[8], g9 = g.v[9];
+  uint32_t g1_19 = 19 * g1, g2_19 = 19 * g2, g3_19 = 19 * g3, g4_19 = 19 * g4, g5_19 = 19 * g5;
+  uint32_t g6_19 = 19 * g6, g7_19 = 19 * g7, g8_19 = 19 * g8, g9_19 = 19 * g9;
+  uint32_t f1_2 = 2 * f1, f3_2 = 2 * f3, f5_2 = 2 * f5, f7_2 = 2 * f7, f9_2 = 2 * f9;
 
-  uint64_t h0 = CMTV_MUL64(f0, g0) + CMTV_MUL64(f1_2, g9_19) + CMTV_MUL64(f2, g8_19) + CMTV_MUL64(f3_2, g7_19) +
-                CMTV_MUL64(f4, g6_19) + CMTV_MUL64(f5_2, g5_19) + CMTV_MUL64(f6, g4_19) + CMTV_MUL64(f7_2, g3_19) +
-                CMTV_MUL64(f8, g2_19) + CMTV_MUL64(f9_2, g1_19);
-  uint64_t h1 = CMTV_MUL64(f0, g1) + CMTV_MUL64(f1, g0) + CMTV_MUL64(f2, g9_19) + CMTV_MUL64(f3, g8_19) +
-                CMTV_MUL64(f4, g7_19) + CMTV_MUL64(f5, g6_19) + CMTV_MUL64(f6, g5_19) + CMTV_MUL64(f7, g4_19) +
-                CMTV_MUL64(f8, g3_19) + CMTV_MUL64(f9, g2_19);
-  uint64_t h2 = CMTV_MUL64(f0, g2) + CMTV_MUL64(f1_2, g1) + CMTV_MUL64(f2, g0) + CMTV_MUL64(f3_2, g9_19) +
-                CMTV_MUL64(f4, g8_19) + CMTV_MUL64(f5_2, g7_19) + CMTV_MUL64(f6, g6_19) + CMTV_MUL64(f7_2, g5_19) +
-                CMTV_MUL64(f8, g4_19) + CMTV_MUL64(f9_2, g3_19);
-  uint64_t h3 = CMTV_MUL64(f0, g3) + CMTV_MUL64(f1, g2) + CMTV_MUL64(f2, g1) + CMTV_MUL64(f3, g0) +
-                CMTV_MUL64(f4, g9_19) + CMTV_MUL64(f5, g8_19) + CMTV_MUL64(f6, g7_19) + CMTV_MUL64(f7, g6_19) +
-                CMTV_MUL64(f8, g5_19) + CMTV_MUL64(f9, g4_19);
-  uint64_t h4 = CMTV_MUL64(f0, g4) + CMTV_MUL64(f1_2, g3) + CMTV_MUL64(f2, g2) + CMTV_MUL64(f3_2, g1) +
-                CMTV_MUL64(f4, g0) + CMTV_MUL64(f5_2, g9_19) + CMTV_MUL64(f6, g8_19) + CMTV_MUL64(f7_2, g7_19) +
-                CMTV_MUL64(f8, g6_19) + CMTV_MUL64(f9_2, g5_19);
-  uint64_t h5 = CMTV_MUL64(f0, g5) + CMTV_MUL64(f1, g4) + CMTV_MUL64(f2, g3) + CMTV_MUL64(f3, g2) +
-                CMTV_MUL64(f4, g1) + CMTV_MUL64(f5, g0) + CMTV_MUL64(f6, g9_19) + CMTV_MUL64(f7, g8_19) +
-                CMTV_MUL64(f8, g7_19) + CMTV_MUL64(f9, g6_19);
-  uint64_t h6 = CMTV_MUL64(f0, g6) + CMTV_MUL64(f1_2, g5) + CMTV_MUL64(f2, g4) + CMTV_MUL64(f3_2, g3) +
-                CMTV_MUL64(f4, g2) + CMTV_MUL64(f5_2, g1) + CMTV_MUL64(f6, g0) + CMTV_MUL64(f7_2, g9_19) +
-                CMTV_MUL64(f8, g8_19) + CMTV_MUL64(f9_2, g7_19);
-  uint64_t h7 = CMTV_MUL64(f0, g7) + CMTV_MUL64(f1, g6) + CMTV_MUL64(f2, g5) + CMTV_MUL64(f3, g4) +
-                CMTV_MUL64(f4, g3) + CMTV_MUL64(f5, g2) + CMTV_MUL64(f6, g1) + CMTV_MUL64(f7, g0) +
-                CMTV_MUL64(f8, g9_19) + CMTV_MUL64(f9, g8_19);
-  uint64_t h8 = CMTV_MUL64(f0, g8) + CMTV_MUL64(f1_2, g7) + CMTV_MUL64(f2, g6) + CMTV_MUL64(f3_2, g5) +
-                CMTV_MUL64(f4, g4) + CMTV_MUL64(f5_2, g3) + CMTV_MUL64(f6, g2) + CMTV_MUL64(f7_2, g1) +
-                CMTV_MUL64(f8, g0) + CMTV_MUL64(f9_2, g9_19);
-  uint64_t h9 = CMTV_MUL64(f0, g9) + CMTV_MUL64(f1, g8) + CMTV_MUL64(f2, g7) + CMTV_MUL64(f3, g6) +
-                CMTV_MUL64(f4, g5) + CMTV_MUL64(f5, g4) + CMTV_MUL64(f6, g3) + CMTV_MUL64(f7, g2) +
-                CMTV_MUL64(f8, g1) + CMTV_MUL64(f9, g0);
-  fe_reduce64(h, h0, h1, h2, h3, h4, h5, h6, h7, h8, h9);
+  const fe_acc_t h0 = fe_column<FE_CHAIN_REF10>(f0, 0, 0, f0, g0, f1_2, g9_19, f2, g8_19, f3_2, g7_19, f4, g6_19,
+                                                      f5_2, g5_19, f6, g4_19, f7_2, g3_19, f8, g2_19, f9_2, g1_19);
+  const fe_acc_t h1 = fe_column<CH>(f0, h0, 26, f0, g1, f1, g0, f2, g9_19, f3, g8_19, f4, g7_19, f5, g6_19, f6, g5_19,
+                                            f7, g4_19, f8, g3_19, f9, g2_19);
+  const fe_acc_t h2 = fe_column<CH>(f0, h1, 25, f0, g2, f1_2, g1, f2, g0, f3_2, g9_19, f4, g8_19, f5_2, g7_19, f6, g6_19,
+                                            f7_2, g5_19, f8, g4_19, f9_2, g3_19);
+  const fe_acc_t h3 = fe_column<CH>(f0, h2, 26, f0, g3, f1, g2, f2, g1, f3, g0, f4, g9_19, f5, g8_19, f6, g7_19,
+                                            f7, g6_19, f8, g5_19, f9, g4_19);
+  const fe_acc_t h4 = fe_column<CH>(f0, h3, 25, f0, g4, f1_2, g3, f2, g2, f3_2, g1, f4, g0, f5_2, g9_19, f6, g8_19,
+                                            f7_2, g7_19, f8, g6_19, f9_2, g5_19);
+  const fe_acc_t h5 = fe_column<CH>(f0, h4, 26, f0, g5, f1, g4, f2, g3, f3, g2, f4, g1, f5, g0, f6, g9_19, f7, g8_19,
+                                            f8, g7_19, f9, g6_19);
+  const fe_acc_t h6 = fe_column<CH>(f0, h5, 25, f0, g6, f1_2, g5, f2, g4, f3_2, g3, f4, g2, f5_2, g1, f6, g0,
+                                            f7_2, g9_19, f8, g8_19, f9_2, g7_19);
+  const fe_acc_t h7 = fe_column<CH>(f0, h6, 26, f0, g7, f1, g6, f2, g5, f3, g4, f4, g3, f5, g2, f6, g1, f7, g0,
+                                            f8, g9_19, f9, g8_19);
+  const fe_acc_t h8 = fe_column<CH>(f0, h7, 25, f0, g8, f1_2, g7, f2, g6, f3_2, g5, f4, g4, f5_2, g3, f6, g2, f7_2, g1,
+                                            f8, g0, f9_2, g9_19);
+  uint32_t lo0 = (uint32_t)h0;  // read again by the wrap
+  const fe_acc_t h9 = fe_column<CH>(lo0, h8, 26, f0, g9, f1, g8, f2, g7, f3, g6, f4, g5, f5, g4, f6, g3, f7, g2, f8, g1,
+                                            f9, g0);
+  fe_finish<CH>(h, lo0, h0, h1, h2, h3, h4, h5, h6, h7, h8, h9);
   CMTV_SCHED_FENCE();
 }
 
+template <fe_chain CH = FE_CHAIN_SERIAL>
 CMTV_HD void fe_sq(fe& h, const fe& f) {
   CMTV_SCHED_FENCE();
 #ifdef CMTV_BOUNDS_CHECK
   for (int i = 0; i < 10; i++) CMTV_ASSERT(f.v[i] < ((i & 1) ? SQ_ODD_BOUND : MUL_BOUND));
 #endif
-  const uint32_t f0 = f.v[0], f1 = f.v[1], f2 = f.v[2], f3 = f.v[3], f4 = f.v[4];
-  const uint32_t f5 = f.v[5], f6 = f.v[6], f7 = f.v[7], f8 = f.v[8], f9 = f.v[9];
-  const uint32_t f0_2 = 2 * f0, f1_2 = 2 * f1, f2_2 = 2 * f2, f3_2 = 2 * f3, f4_2 = 2 * f4;
-  const uint32_t f5_2 = 2 * f5, f6_2 = 2 * f6, f7_2 = 2 * f7;
-  const uint32_t f5_38 = 38 * f5, f6_19 = 19 * f6, f7_38 = 38 * f7, f8_19 = 19 * f8, f9_38 = 38 * f9;
+  uint32_t f0 = f.v[0], f1 = f.v[1], f2 = f.v[2], f3 = f.v[3], f4 = f.v[4];
+  uint32_t f5 = f.v[5], f6 = f.v[6], f7 = f.v[7], f8 = f.v[8], f9 = f.v[9];
+  uint32_t f0_2 = 2 * f0, f1_2 = 2 * f1, f2_2 = 2 * f2, f3_2 = 2 * f3, f4_2 = 2 * f4;
+  uint32_t f5_2 = 2 * f5, f6_2 = 2 * f6, f7_2 = 2 * f7;
+  uint32_t f5_38 = 38 * f5, f6_19 = 19 * f6, f7_38 = 38 * f7, f8_19 = 19 * f8, f9_38 = 38 * f9;
 
-  uint64_t h0 = CMTV_MUL64(f0, f0) + CMTV_MUL64(f1_2, f9_38) + CMTV_MUL64(f2_2, f8_19) + CMTV_MUL64(f3_2, f7_38) +
-                CMTV_MUL64(f4_2, f6_19) + CMTV_MUL64(f5, f5_38);
-  uint64_t h1 = CMTV_MUL64(f0_2, f1) + CMTV_MUL64(f2, f9_38) + CMTV_MUL64(f3_2, f8_19) + CMTV_MUL64(f4, f7_38) +
-                CMTV_MUL64(f5_2, f6_19);
-  uint64_t h2 = CMTV_MUL64(f0_2, f2) + CMTV_MUL64(f1_2, f1) + CMTV_MUL64(f3_2, f9_38) + CMTV_MUL64(f4_2, f8_19) +
-                CMTV_MUL64(f5_2, f7_38) + CMTV_MUL64(f6, f6_19);
-  uint64_t h3 = CMTV_MUL64(f0_2, f3) + CMTV_MUL64(f1_2, f2) + CMTV_MUL64(f4, f9_38) + CMTV_MUL64(f5_2, f8_19) +
-                CMTV_MUL64(f6, f7_38);
-  uint64_t h4 = CMTV_MUL64(f0_2, f4) + CMTV_MUL64(f1_2, f3_2) + CMTV_MUL64(f2, f2) + CMTV_MUL64(f5_2, f9_38) +
-                CMTV_MUL64(f6_2, f8_19) + CMTV_MUL64(f7, f7_38);
-  uint64_t h5 = CMTV_MUL64(f0_2, f5) + CMTV_MUL64(f1_2, f4) + CMTV_MUL64(f2_2, f3) + CMTV_MUL64(f6, f9_38) +
-                CMTV_MUL64(f7_2, f8_19);
-  uint64_t h6 = CMTV_MUL64(f0_2, f6) + CMTV_MUL64(f1_2, f5_2) + CMTV_MUL64(f2_2, f4) + CMTV_MUL64(f3_2, f3) +
-                CMTV_MUL64(f7_2, f9_38) + CMTV_MUL64(f8, f8_19);
-  uint64_t h7 = CMTV_MUL64(f0_2, f7) + CMTV_MUL64(f1_2, f6) + CMTV_MUL64(f2_2, f5) + CMTV_MUL64(f3_2, f4) +
-                CMTV_MUL64(f8, f9_38);
-  uint64_t h8 = CMTV_MUL64(f0_2, f8) + CMTV_MUL64(f1_2, f7_2) + CMTV_MUL64(f2_2, f6) + CMTV_MUL64(f3_2, f5_2) +
-                CMTV_MUL64(f4, f4) + CMTV_MUL64(f9, f9_38);
-  uint64_t h9 = CMTV_MUL64(f0_2, f9) + CMTV_MUL64(f1_2, f8) + CMTV_MUL64(f2_2, f7) + CMTV_MUL64(f3_2, f6) +
-                CMTV_MUL64(f4_2, f5);
-  fe_reduce64(h, h0, h1, h2, h3, h4, h5, h6, h7, h8, h9);
+  const fe_acc_t h0 = fe_column<FE_CHAIN_REF10>(f0_2, 0, 0, f0, f0, f1_2, f9_38, f2_2, f8_19, f3_2, f7_38, f4_2, f6_19,
+                                                      f5, f5_38);
+  const fe_acc_t h1 = fe_column<CH>(f0_2, h0, 26, f0_2, f1, f2, f9_38, f3_2, f8_19, f4, f7_38, f5_2, f6_19);
+  const fe_acc_t h2 = fe_column<CH>(f0_2, h1, 25, f0_2, f2, f1_2, f1, f3_2, f9_38, f4_2, f8_19, f5_2, f7_38, f6, f6_19);
+  const fe_acc_t h3 = fe_column<CH>(f0_2, h2, 26, f0_2, f3, f1_2, f2, f4, f9_38, f5_2, f8_19, f6, f7_38);
+  const fe_acc_t h4 = fe_column<CH>(f0_2, h3, 25, f0_2, f4, f1_2, f3_2, f2, f2, f5_2, f9_38, f6_2, f8_19, f7, f7_38);
+  const fe_acc_t h5 = fe_column<CH>(f0_2, h4, 26, f0_2, f5, f1_2, f4, f2_2, f3, f6, f9_38, f7_2, f8_19);
+  const fe_acc_t h6 = fe_column<CH>(f0_2, h5, 25, f0_2, f6, f1_2, f5_2, f2_2, f4, f3_2, f3, f7_2, f9_38, f8, f8_19);
+  const fe_acc_t h7 = fe_column<CH>(f0_2, h6, 26, f0_2, f7, f1_2, f6, f2_2, f5, f3_2, f4, f8, f9_38);
+  const fe_acc_t h8 = fe_column<CH>(f0_2, h7, 25, f0_2, f8, f1_2, f7_2, f2_2, f6, f3_2, f5_2, f4, f4, f9, f9_38);
+  uint32_t lo0 = (uint32_t)h0;  // read again by the wrap
+  const fe_acc_t h9 = fe_column<CH>(lo0, h8, 26, f0_2, f9, f1_2, f8, f2_2, f7, f3_2, f6, f4_2, f5);
+  fe_finish<CH>(h, lo0, h0, h1, h2, h3, h4, h5, h6, h7, h8, h9);
   CMTV_SCHED_FENCE();
 }
 
@@ -237,13 +334,14 @@ CMTV_HD void fe_sq(fe& h, const fe& f) {
 // optimiser: with a constant n (every call site) LLVM rotates the loop and
 // splits the 64-bit column sums, 129 VALU instructions per squaring instead of
 // 107 (gfx950 listing) -- a fifth of the square-root chains' cost.
+template <fe_chain CH = FE_CHAIN_SERIAL>
 CMTV_HD void fe_sqn(fe& h, const fe& f, int n) {
 #if defined(__HIP_DEVICE_COMPILE__)
   asm volatile("" : "+s"(n));
 #endif
-  fe_sq(h, f);
+  fe_sq<CH>(h, f);
 #pragma unroll 1
-  for (int i = 1; i < n; i++) fe_sq(h, h);
+  for (int i = 1; i < n; i++) fe_sq<CH>(h, h);
 }
 
 // load 255 bits (bit 255 ignored) from 8 little-endian 32-bit words; the value

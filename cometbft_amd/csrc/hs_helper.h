@@ -32,10 +32,13 @@ constexpr uint32_t kHsTabU2 = 2 * 9 * 5 * 64;
 // to the quads: X, Y, Z, 10 words each
 constexpr uint32_t kHsPsWords = 30;
 // ... and the comb positions of [s]B that wave adds (the top ones; the quads
-// add the rest before they wait for it); CMTV_HS_PRE overrides it. All 16:
-// 15, 14 and 13 measured 0.3%, 0.8% and 1.4% slower (profiles/
-// r07_hs_fold_ab.txt), with the sign-bytes fused as well
-constexpr int kHsFoldCombPre = 16;
+// add the rest before they wait for it); CMTV_HS_PRE overrides it. 15 since
+// the serial carry chain shortened the quads' decode and tables more than the
+// comb wave's additions, so that the quads came to the flag 11k cycles before
+// P_s: 15 and 14 measure 1.4% faster than all 16, 13 1.0% (profiles/
+// r08_fe_carry_ab.txt; before it 15, 14 and 13 were 0.3%, 0.8% and 1.4%
+// slower than 16, profiles/r07_hs_fold_ab.txt)
+constexpr int kHsFoldCombPre = 15;
 
 // the number of [u]B's comb positions the helper takes (launcher's hs_tune
 // bits 0..7: CMTV_HS_PRE + 1; 0 = the kernel's default)

@@ -182,7 +182,7 @@ __global__ __launch_bounds__(256, CMTV_QUAD_WAVES_PER_EU) void k_verify_quad_hs(
 // The helper reaches barrier 1 some 56k cycles before the quads even with
 // the comb beside it, so the comb fills that SIMD's slack; beside a quad wave
 // the same comb costs the kernel 12%. The comb wave takes the top
-// kHsFoldCombPre positions (all 16, measured best; CMTV_HS_PRE overrides it)
+// kHsFoldCombPre positions (15 of the 16, measured best; CMTV_HS_PRE overrides it)
 // and the quads add the rest themselves before they look at the flag.
 //
 // P_s travels as (X, Y, Z), 30 words a signature, in the tail of xbuf: the
