@@ -48,7 +48,7 @@ COMMIT_PANIC_UNKNOWN_FLAG = 9
 # every symbol include/cmtverify.h declares (checked by tests/test_abi.py)
 EXPORTS = (
     "cmtv_open", "cmtv_open_devices", "cmtv_device_count", "cmtv_device_ordinal", "cmtv_device_stream", "cmtv_sync",
-    "cmtv_verify_ed25519_sharded_device", "cmtv_verify_ed25519_indexed_sharded_device", "cmtv_verify_ed25519_multi_device", "cmtv_close", "cmtv_strerror", "cmtv_abi_version", "cmtv_stats_get", "cmtv_device_stats_get", "cmtv_stream",
+    "cmtv_verify_ed25519_sharded_device", "cmtv_verify_ed25519_indexed_sharded_device", "cmtv_verify_ed25519_multi_device", "cmtv_close", "cmtv_strerror", "cmtv_abi_version", "cmtv_stats_get", "cmtv_late_sum_waves", "cmtv_device_stats_get", "cmtv_stream",
     "cmtv_verify_ed25519", "cmtv_verify_ed25519_device", "cmtv_verify_sr25519", "cmtv_verify_sr25519_device",
     "cmtv_verify_secp256k1", "cmtv_verify_secp256k1_device",
     "cmtv_register_keys_secp256k1", "cmtv_secp_keyset_free", "cmtv_secp_keyset_len", "cmtv_verify_secp256k1_indexed",
@@ -166,6 +166,10 @@ def lib() -> ctypes.CDLL:
     L.cmtv_stats_get.restype = ctypes.c_int
     L.cmtv_device_stats_get.argtypes = [vp, ctypes.c_int, ctypes.POINTER(cmtv_device_stats)]
     L.cmtv_device_stats_get.restype = ctypes.c_int
+    # (an older build loaded through CMTV_LIBRARY for an A/B does not have it)
+    if hasattr(L, "cmtv_late_sum_waves"):
+        L.cmtv_late_sum_waves.argtypes = [vp, ctypes.POINTER(u64)]
+        L.cmtv_late_sum_waves.restype = ctypes.c_int
     L.cmtv_stream.argtypes = [vp]
     L.cmtv_stream.restype = vp
     L.cmtv_verify_ed25519.argtypes = [vp, sz, _u8p, _u8p, _u8p, u32p, u32, _u8p, ctypes.POINTER(u64)]

@@ -125,7 +125,13 @@ class Context:
     def stats(self) -> dict:
         st = N.cmtv_stats()
         N.check(N.lib().cmtv_stats_get(self._h, ctypes.byref(st)), "cmtv_stats_get")
-        return {k: getattr(st, k) for k, _ in st._fields_ if k != "reserved"}
+        out = {k: getattr(st, k) for k, _ in st._fields_ if k != "reserved"}
+        # a counter of its own call: cmtv_stats keeps its layout
+        late_sum = ctypes.c_uint64(0)
+        if hasattr(N.lib(), "cmtv_late_sum_waves"):
+            N.check(N.lib().cmtv_late_sum_waves(self._h, ctypes.byref(late_sum)), "cmtv_late_sum_waves")
+        out["late_sum_waves"] = late_sum.value
+        return out
 
     def device_stats(self) -> list:
         """cmtv_device_stats_get for every device of the context: ordinal,

@@ -460,8 +460,11 @@ CMTV_HD void hs_bscalar(uint32_t u[8], const uint32_t k2mag[8], bool neg, const 
 CMTV_HD void hs_digits16(uint32_t t[8], const uint32_t x[8], int W) {
   uint32_t a[8], b[8];
   sc_bias(a, x, 0x88888888u);
-  // W nibbles of 8: words 0-3 whole, word 4 holds W - 32 (1..5) of them
-  const uint32_t w4 = 0x88888888u & ((1u << (4 * (W - 32))) - 1u);
+  // W nibbles of 8: words 0-3 whole, word 4 holds W - 32 (1..5) of them (the
+  // wide schedule takes a below, so its count is clamped only to keep the
+  // shift defined)
+  const int Wn = W > HS_MAX_WINDOWS ? HS_MAX_WINDOWS : W;
+  const uint32_t w4 = 0x88888888u & ((1u << (4 * (Wn - 32))) - 1u);
   uint64_t c = 0;
 #pragma unroll
   for (int i = 0; i < 8; i++) {
@@ -471,7 +474,7 @@ CMTV_HD void hs_digits16(uint32_t t[8], const uint32_t x[8], int W) {
     c = v >> 32;
   }
   // b < 2^(4W): shift left by 4 (64 - W) = 96 + bs bits, bs = 4 (40 - W) in 12..28
-  const int bs = 4 * (40 - (W > HS_MAX_WINDOWS ? HS_MAX_WINDOWS : W));
+  const int bs = 4 * (40 - Wn);
 #pragma unroll
   for (int i = 0; i < 8; i++) {
     const uint32_t hi = i >= 3 ? b[i - 3] : 0u;

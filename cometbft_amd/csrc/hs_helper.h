@@ -57,17 +57,53 @@ __device__ __forceinline__ int hs_workgroup_windows(uint32_t flags, uint32_t t) 
   return wide ? HS_WIDE_WINDOWS : W;
 }
 
-// lane t < 48 writes its signature's four cached coordinates out[0..3] where
-// the quads' hs_slot_load finds them
-__device__ __forceinline__ void hs_slot_store(uint2* dst, uint32_t t, const fe* out) {
+// lane t < 48 writes coordinate c of its signature's cached sum where the
+// quads' hs_slot_load finds it
+__device__ __forceinline__ void hs_slot_store_coord(uint2* dst, uint32_t t, int c, const fe& v) {
   if (t < 48) {
 #pragma unroll
-    for (int c = 0; c < 4; c++)
-#pragma unroll
-      for (int k = 0; k < 5; k++)
-        dst[(t >> 4) * 320 + k * 64 + 4 * (t & 15) + c] = make_uint2(out[c].v[2 * k], out[c].v[2 * k + 1]);
+    for (int k = 0; k < 5; k++) dst[(t >> 4) * 320 + k * 64 + 4 * (t & 15) + c] = make_uint2(v.v[2 * k], v.v[2 * k + 1]);
   }
 }
+
+// ... and all four, out[0..3]
+__device__ __forceinline__ void hs_slot_store(uint2* dst, uint32_t t, const fe* out) {
+#pragma unroll
+  for (int c = 0; c < 4; c++) hs_slot_store_coord(dst, t, c, out[c]);
+}
+
+// A helper lane's walk down its signature's windows after barrier 1: the
+// digits of k1 and k2 from window W-2 down (the top window is the quads' own)
+// and the read of the quads' tables h_window_addend takes. tabs = the
+// workgroup's three quad waves' tables; lane t < 48 owns signature t (quad
+// wave t >> 4, quad t & 15).
+struct HsWalk {
+  uint32_t tA[8], tR[8];
+  const uint2* tw;
+  bool r_flip;
+  __device__ __forceinline__ HsWalk(const SigPrep& p, int W, const uint2* tabs, uint32_t t) {
+    const uint32_t slot = t < 48 ? t : 47;
+    r_flip = (p.flags & 1u) != 0;
+    hs_digits16(tA, p.k1, W);
+    hs_digits16(tR, p.k2, W);
+    sc_shift_out(tA, 4);
+    sc_shift_out(tR, 4);
+    tw = tabs + (slot >> 4) * kHsTabU2 + 4 * (slot & 15);
+  }
+  __device__ __forceinline__ void next(int& dA, int& dR) {
+    dA = (int)sc_shift_out(tA, 4) - 8;
+    dR = (int)sc_shift_out(tR, 4) - 8;
+  }
+  __device__ __forceinline__ void operator()(int P, int e, int c, fe& r) const {
+    const uint2* src = tw + (P * 9 + e) * 5 * 64 + c;
+#pragma unroll
+    for (int k = 0; k < 5; k++) {
+      const uint2 x = src[k * 64];
+      r.v[2 * k] = x.x;
+      r.v[2 * k + 1] = x.y;
+    }
+  }
+};
 
 // After barrier 1: windows W-2 .. 0 (the top one is the quads'), each sum
 // written to ring slot (win & 1) before that window's barrier (a slot is
@@ -80,35 +116,110 @@ __device__ __forceinline__ void hs_slot_store(uint2* dst, uint32_t t, const fe* 
 template <class Clock>
 __device__ __forceinline__ void hs_helper_sums(const SigPrep& p, int W, const uint2* tabs, uint2* ring, uint32_t t,
                                                const Clock& clock, uint64_t& hwait) {
-  const uint32_t slot = t < 48 ? t : 47;
-  const bool r_flip = (p.flags & 1u) != 0;
-  uint32_t tA[8], tR[8];
-  hs_digits16(tA, p.k1, W);
-  hs_digits16(tR, p.k2, W);
-  sc_shift_out(tA, 4);  // the top window is the quads' own
-  sc_shift_out(tR, 4);
-  const uint2* tw = tabs + (slot >> 4) * kHsTabU2;
-  const uint32_t qb = 4 * (slot & 15);
-  auto rd = [&](int P, int e, int c, fe& r) {
-    const uint2* src = tw + (P * 9 + e) * 5 * 64 + qb + c;
-#pragma unroll
-    for (int k = 0; k < 5; k++) {
-      const uint2 x = src[k * 64];
-      r.v[2 * k] = x.x;
-      r.v[2 * k + 1] = x.y;
-    }
-  };
+  HsWalk rd(p, W, tabs, t);
 #pragma unroll 1
   for (int win = W - 2; win >= 0; win--) {
-    const int dA = (int)sc_shift_out(tA, 4) - 8;
-    const int dR = (int)sc_shift_out(tR, 4) - 8;
+    int dA, dR;
+    rd.next(dA, dR);
     fe out[4];
-    h_window_addend(out, rd, dA, dR, r_flip);
+    h_window_addend(out, rd, dA, dR, rd.r_flip);
     hs_slot_store(ring + (win & 1) * kHsSlotU2, t, out);
     const uint64_t c0 = clock();
     __syncthreads();  // window win
     hwait += clock() - c0;
   }
+}
+
+// hs_helper_sums split over the two waves of the folded form's helper SIMD
+// (k_verify_quad_hs_fold): the hash helper runs hs_helper_sums_eh and the comb
+// wave hs_helper_sums_fg, on the same lanes, digits and table reads. Per
+// window the comb wave computes F, G and the sum's 2Z (quad.h
+// h_window_addend_fg), writes 2Z to the ring slot and F and G to the exchange
+// area fg (kHsFgU2 uint2: word pair k of F at [k * 48 + t], of G at
+// [(5 + k) * 48 + t]), and publishes the window's index in *fg_ready behind a
+// release fence; the hash helper computes E, H and 2dT (h_window_addend_eh),
+// takes F and G once *fg_ready names its window, and finishes Y-X and Y+X
+// (h_window_addend_xy). Both meet every window barrier, W - 1 in all.
+//
+// fg_wait bounds the hash helper's poll, so the wait never decides a verdict:
+// when it runs out the helper computes the whole of h_window_addend for that
+// window itself (the comb wave may still store the same 2Z later, before the
+// window's barrier) and hs_helper_sums_eh returns true. fg_wait = 0: it never
+// polls, and the comb wave is expected to idle at the barriers instead.
+constexpr uint32_t kHsFgU2 = 2 * 5 * 48;
+constexpr uint32_t kHsFgNone = 0xFFFFFFFFu;  // *fg_ready before the first window
+
+__device__ __forceinline__ void hs_helper_sums_fg(const SigPrep& p, int W, const uint2* tabs, uint2* ring, uint2* fg,
+                                                  uint32_t* fg_ready, uint32_t t) {
+  HsWalk rd(p, W, tabs, t);
+#pragma unroll 1
+  for (int win = W - 2; win >= 0; win--) {
+    int dA, dR;
+    rd.next(dA, dR);
+    fe z2, f, g;
+    h_window_addend_fg(z2, f, g, rd, dA, dR, rd.r_flip);
+    if (t < 48) {
+#pragma unroll
+      for (int k = 0; k < 5; k++) {
+        fg[k * 48 + t] = make_uint2(f.v[2 * k], f.v[2 * k + 1]);
+        fg[(5 + k) * 48 + t] = make_uint2(g.v[2 * k], g.v[2 * k + 1]);
+      }
+    }
+    hs_slot_store_coord(ring + (win & 1) * kHsSlotU2, t, 2, z2);
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+    if (t == 0) __hip_atomic_store(fg_ready, (uint32_t)win, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    __syncthreads();  // window win
+  }
+}
+
+// fwait: cycles at the poll when clock() counts them (the probe build)
+template <class Clock>
+__device__ __forceinline__ bool hs_helper_sums_eh(const SigPrep& p, int W, const uint2* tabs, uint2* ring,
+                                                  const uint2* fg, uint32_t* fg_ready, uint32_t fg_wait, uint32_t t,
+                                                  const Clock& clock, uint64_t& hwait, uint64_t& fwait) {
+  HsWalk rd(p, W, tabs, t);
+  const uint32_t slot = t < 48 ? t : 47;
+  bool late = false;
+#pragma unroll 1
+  for (int win = W - 2; win >= 0; win--) {
+    int dA, dR;
+    rd.next(dA, dR);
+    uint2* dst = ring + (win & 1) * kHsSlotU2;
+    fe out[4], e, h;
+    h_window_addend_eh(out[3], e, h, rd, dA, dR, rd.r_flip);
+    const uint64_t f0 = clock();
+    bool ready = false;
+    for (uint32_t spins = 0; spins < fg_wait; spins++) {
+      ready = __hip_atomic_load(fg_ready, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) == (uint32_t)win;
+      if (ready) break;
+      __builtin_amdgcn_s_sleep(1);
+    }
+    fwait += clock() - f0;
+    if (__builtin_expect(__ballot(ready) != __ballot(1), 0)) {
+      late = true;
+      h_window_addend(out, rd, dA, dR, rd.r_flip);
+      hs_slot_store(dst, t, out);
+    } else {
+      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+      fe f, g;
+#pragma unroll
+      for (int k = 0; k < 5; k++) {
+        const uint2 a = fg[k * 48 + slot], b = fg[(5 + k) * 48 + slot];
+        f.v[2 * k] = a.x;
+        f.v[2 * k + 1] = a.y;
+        g.v[2 * k] = b.x;
+        g.v[2 * k + 1] = b.y;
+      }
+      h_window_addend_xy(out[0], out[1], e, f, g, h);
+      hs_slot_store_coord(dst, t, 0, out[0]);
+      hs_slot_store_coord(dst, t, 1, out[1]);
+      hs_slot_store_coord(dst, t, 3, out[3]);
+    }
+    const uint64_t c0 = clock();
+    __syncthreads();  // window win
+    hwait += clock() - c0;
+  }
+  return late;
 }
 
 // hs_helper_sums, then [u]B's partial sum bc.P in slot 1 before the last

@@ -29,11 +29,15 @@ constexpr uint32_t kCombScratchWordsPerKey = 128 * 320;  // prefix products whil
 // sr25519 has the lane and quad forms. kLaunchForceWide: the CMTV_FORCE_WIDE
 // test knob (every quad-family verifier takes the 64-window schedule); bits
 // 16..31: the helper-summed forms' tuning (hs_tune: CMTV_HS_PRE in its bits
-// 0..7, CMTV_HS_FOLD_TUNE in bits 8..10). kLaunchHsFold: the Ed25519 quad form
+// 0..7, CMTV_HS_FOLD_TUNE in bits 8..10, kHsTune* above them). kLaunchHsFold: the Ed25519 quad form
 // runs k_verify_quad_hs_fold ([s]B folded into R by a fifth wave) instead of
 // k_verify_quad_hs.
 constexpr uint32_t kFormLane = 0, kFormQuad = 1, kFormOct2 = 2, kFormRow = 3, kFormRow4 = 4;
 constexpr uint32_t kFormMask = 0xFF, kLaunchForceWide = 0x100, kLaunchHsFold = 0x200;
+// hs_tune bits 11 and 12, k_verify_quad_hs_fold only: the window sums are
+// split over the hash helper and the comb wave (CMTV_HS_SUM_SPLIT); the comb
+// wave's half never arrives (the CMTV_FORCE_FG_LATE test knob)
+constexpr uint32_t kHsTuneSumSplit = 1u << 11, kHsTuneFgLate = 1u << 12;
 // registered-key forms (launch_verify_keyed): the keyed row kernel
 // (k_verify_keyed_row_split, one signature per workgroup), the keyed quad
 // kernel with two helper waves (k_verify_keyed_quad_split), the lane kernels
@@ -85,8 +89,10 @@ constexpr uint32_t kSbFuseMaxMsg = 192;
 // hashed their own signatures. kKeyedWaitDefault = the polls before that.
 // kDiagLatePs = quad waves of k_verify_quad_hs_fold that stopped waiting for
 // the comb wave's [s]B and added the comb rows themselves, after kPsWaitDefault
-// polls.
-constexpr uint32_t kDiagLateK = 0, kDiagLatePs = 1, kDiagWords = 4;
+// polls. kDiagLateSum = workgroups of that kernel whose hash helper stopped
+// waiting for the comb wave's half of a window sum at least once and formed
+// the sum alone (at most one count per workgroup and launch).
+constexpr uint32_t kDiagLateK = 0, kDiagLatePs = 1, kDiagLateSum = 2, kDiagWords = 4;
 constexpr uint32_t kKeyedWaitDefault = 1u << 22, kPsWaitDefault = 1u << 22;
 
 hipError_t launch_btab_init(uint32_t* d_rows, hipStream_t s);

@@ -203,6 +203,19 @@ __global__ __launch_bounds__(256, CMTV_QUAD_WAVES_PER_EU) void k_verify_quad_hs(
 // (CMTV_HS_FOLD_TUNE): 1 = the hash helper is wave 3 and the quads waves 0-2
 // (the comb then shares a quad's SIMD), 2 / 4 = the comb wave at issue
 // priority 0 / 3.
+//
+// After barrier 1 the helper's SIMD decides the window barriers when one wave
+// forms S_w alone at the lone-wave issue rate, so with hs_tune's
+// kHsTuneSumSplit (CMTV_HS_SUM_SPLIT=1; off by default, it measured a tie:
+// DESIGN.md 5 round 9) the two waves of that SIMD share every
+// window's sum (hs_helper.h hs_helper_sums_eh / _fg): the comb wave takes the
+// T and Z half (F, G, 2Z; the scalars from prep), the hash helper the X and Y
+// half and the last two products, F and G crossing through fgx. The helper's
+// poll for them is bounded like the quads' for P_s: when it runs out the
+// helper forms the whole sum itself, and the workgroup counts once in
+// diag[kDiagLateSum] (cmtv_late_sum_waves); kHsTuneFgLate (the
+// CMTV_FORCE_FG_LATE test knob) makes the comb wave idle and every window take
+// that path.
 template <uint32_t MODE>
 __global__ __launch_bounds__(320, 1) void k_verify_quad_hs_fold(
     uint32_t n, const uint32_t* __restrict__ pk, const uint32_t* __restrict__ sig, const uint8_t* __restrict__ msg,
@@ -215,20 +228,36 @@ __global__ __launch_bounds__(320, 1) void k_verify_quad_hs_fold(
   const uint32_t tune = hs_tune >> 8;
   const int comb_pre = hs_comb_pre(hs_tune, kHsFoldCombPre);
   const uint32_t helper_wave = (tune & 1u) ? 3u : 0u;
+  // the window sums split over the helper and the comb wave; not with the
+  // helper on wave 3, where the comb wave's share would take a quad's issue slots
+  const bool sum_split = (hs_tune & kHsTuneSumSplit) != 0 && helper_wave == 0;
+  const bool fg_late = (hs_tune & kHsTuneFgLate) != 0;
   __shared__ uint32_t prep[48][SIG_PREP_WORDS + 1];
   __shared__ uint2 tab_lds[3][kHsTabU2];
   __shared__ uint2 xbuf[2 * kHsSlotU2];  // sign-bytes | P_s, then the 2-slot ring
   __shared__ uint32_t ps_ready;
+  // F and G of the window in flight, from the comb wave to the hash helper
+  // (hs_helper.h hs_helper_sums_fg / _eh), and the index of the window they
+  // belong to. One copy is enough, and the window barrier is its only reuse
+  // fence: the comb wave writes window w-1's F and G only after barrier w, and
+  // the helper has read window w's before it reaches barrier w.
+  __shared__ uint2 fgx[kHsFgU2];
+  __shared__ uint32_t fg_ready;
   static_assert(sizeof(xbuf) >= 48 * (kSbFuseMaxMsg + 4 * kHsPsWords), "P_s goes behind the sign-bytes buffer");
+  static_assert(sizeof(prep) + sizeof(tab_lds) + sizeof(xbuf) + sizeof(fgx) + 2 * sizeof(uint32_t) <= 160 * 1024,
+                "a workgroup's LDS");
   uint32_t* pspt = reinterpret_cast<uint32_t*>(xbuf) + 48 * (kSbFuseMaxMsg / 4);
   // probe slots: 0 entry, 6 HW_ID; 1 / 2 before / after barrier 1; comb wave
   // 3 = P_s published; helper 3 = its last sum, 7 = cycles at the window
-  // barriers; quads 4 = P_s taken, 3 = cycles at the flag, 5 = exit, 7 as the
-  // helper
+  // barriers, 4 = cycles at its polls for F and G; quads 4 = P_s taken,
+  // 3 = cycles at the flag, 5 = exit, 7 as the helper
   CMTV_STAMP5(0);
   CMTV_HWID5();
-  if (threadIdx.x == 0) ps_ready = 0u;
-  __syncthreads();  // the flag is clear before any wave can set or read it
+  if (threadIdx.x == 0) {
+    ps_ready = 0u;
+    fg_ready = kHsFgNone;
+  }
+  __syncthreads();  // the flags are clear before any wave can set or read them
   if (hw == 4) {
     if (tune & 2u) __builtin_amdgcn_s_setprio(0);
     if (tune & 4u) __builtin_amdgcn_s_setprio(3);
@@ -259,6 +288,12 @@ __global__ __launch_bounds__(320, 1) void k_verify_quad_hs_fold(
     __syncthreads();  // 1
     CMTV_STAMP5(2);
     const int W = (int)__builtin_amdgcn_readfirstlane((prep[0][24] >> 16) & 0xFFu);
+    if (sum_split && !fg_late) {
+      SigPrep p;
+      sig_prep_load_pair(p, prep[t < 48 ? t : 47]);
+      hs_helper_sums_fg(p, W, &tab_lds[0][0], xbuf, fgx, &fg_ready, t);
+      return;
+    }
 #pragma unroll 1
     for (int win = W - 2; win >= 0; win--) __syncthreads();  // window win
     return;
@@ -278,8 +313,17 @@ __global__ __launch_bounds__(320, 1) void k_verify_quad_hs_fold(
     CMTV_STAMP5(1);
     __syncthreads();  // 1: the scalars; the tables are built
     CMTV_STAMP5(2);
-    uint64_t hwait = 0;  // probe build: cycles the helper waits at the window barriers
-    hs_helper_sums(p, W, &tab_lds[0][0], xbuf, t, [] { return (uint64_t)CMTV_CLOCK(); }, hwait);
+    uint64_t hwait = 0, fwait = 0;  // probe build: cycles the helper waits at the window barriers, for F and G
+    (void)fwait;
+    auto clock = [] { return (uint64_t)CMTV_CLOCK(); };
+    if (sum_split) {
+      const bool late = hs_helper_sums_eh(p, W, &tab_lds[0][0], xbuf, fgx, &fg_ready, fg_late ? 0u : kPsWaitDefault, t,
+                                          clock, hwait, fwait);
+      if (late && t == 0 && diag) atomicAdd(diag + kDiagLateSum, 1u);
+    } else {
+      hs_helper_sums(p, W, &tab_lds[0][0], xbuf, t, clock, hwait);
+    }
+    CMTV_STAMP5_VAL(4, fwait);
     CMTV_STAMP5_VAL(7, hwait);
     CMTV_STAMP5(3);
     return;

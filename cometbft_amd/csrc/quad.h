@@ -845,6 +845,72 @@ CMTV_HD void h_window_addend(fe out[4], const Rd& rd, int dA, int dR, bool r_fli
   fe_mul(out[3], T3, m);
 }
 
+// h_window_addend in three pieces, for two waves that share one window's sum
+// (hs_helper.h hs_helper_sums_eh / hs_helper_sums_fg): the same formulas on
+// the same operands in the same order, so every limb of out[0..3] is
+// h_window_addend's. _eh reads X and Y of both entries (4 multiplications:
+// A, B, T3 = E H, out[3] = 2d T3) and keeps E and H; _fg reads T and Z
+// (4 multiplications: 2d T2, C, D, Z3 = F G; out[2] = 2 Z3) and hands F and G
+// on; _xy finishes (2 multiplications: X3 = E F, Y3 = G H).
+template <class Rd>
+CMTV_HD void h_window_addend_eh(fe& out3, fe& e, fe& h, const Rd& rd, int dA, int dR, bool r_flip) {
+  const int eA = dA < 0 ? -dA : dA, eR = dR < 0 ? -dR : dR;
+  const bool nA = dA < 0, nR = (dR < 0) != r_flip;
+  fe x, y, s, d, m, s2, d2;
+  rd(0, eA, 0, x);
+  rd(0, eA, 1, y);
+  fe_sub(d, y, x);  // Y1 - X1
+  fe_add(s, y, x);  // Y1 + X1
+  rd(1, eR, 0, x);
+  rd(1, eR, 1, y);
+  fe_sub(d2, y, x);  // Y2 - X2
+  fe_add(s2, y, x);  // Y2 + X2
+  fe_select(x, d, s, nA);
+  fe_select(m, d2, s2, nR);
+  fe_mul(x, x, m);  // A
+  fe_select(y, s, d, nA);
+  fe_select(m, s2, d2, nR);
+  fe_mul(y, y, m);  // B
+  fe_sub(e, y, x);  // E = B - A
+  fe_add(h, y, x);  // H = B + A
+  fe T3;
+  fe_mul(T3, e, h);
+  fe_const_d2(m);
+  fe_mul(out3, T3, m);
+}
+
+template <class Rd>
+CMTV_HD void h_window_addend_fg(fe& out2, fe& f, fe& g, const Rd& rd, int dA, int dR, bool r_flip) {
+  const int eA = dA < 0 ? -dA : dA, eR = dR < 0 ? -dR : dR;
+  const bool nA = dA < 0, nR = (dR < 0) != r_flip;
+  fe x, y, s, d, m, d2;
+  rd(1, eR, 3, m);
+  fe_const_d2(d2);
+  fe_mul(m, m, d2);  // 2d T2
+  rd(0, eA, 3, x);
+  fe_mul(x, x, m);  // +/- C = T1 2dT2
+  rd(0, eA, 2, y);
+  rd(1, eR, 2, m);
+  fe_add(m, m, m);
+  fe_mul(y, y, m);  // D = Z1 2Z2
+  fe_add(s, y, x);  // D + C
+  fe_sub(d, y, x);  // D - C
+  const bool cneg = nA != nR;
+  fe_select(f, d, s, cneg);  // F = D - C
+  fe_select(g, s, d, cneg);  // G = D + C
+  fe Z3;
+  fe_mul(Z3, f, g);
+  fe_add(out2, Z3, Z3);
+}
+
+CMTV_HD void h_window_addend_xy(fe& out0, fe& out1, const fe& e, const fe& f, const fe& g, const fe& h) {
+  fe X3, Y3;
+  fe_mul(X3, e, f);
+  fe_mul(Y3, g, h);
+  fe_sub(out0, Y3, X3);
+  fe_add(out1, Y3, X3);
+}
+
 // The quad side of the helper-summed verifiers after the decode (v: this
 // lane's coordinate of -A, rc: of -R, both extended, Z = 1): both tables,
 // then get_prep (the scalars; flags bits 16..23 carry the window count W the

@@ -267,6 +267,9 @@ static void read_env(cmtv_ctx* ctx) {
   if (const char* kl = std::getenv("CMTV_FORCE_K_LATE")) ctx->keyed_wait = kl[0] == '1' ? 0u : kKeyedWaitDefault;
   env_not("CMTV_HS_FOLD", '0', ctx->hs_fold);
   if (const char* pl = std::getenv("CMTV_FORCE_PS_LATE")) ctx->ps_wait = pl[0] == '1' ? 0u : kPsWaitDefault;
+  env_not("CMTV_HS_SUM_SPLIT", '0', ctx->hs_sum_split);
+  env_is("CMTV_FORCE_FG_LATE", '1', ctx->fg_late);
+  if (ctx->fg_late && !std::getenv("CMTV_HS_SUM_SPLIT")) ctx->hs_sum_split = true;
   {
     uint32_t ft = 0;
     env_int("CMTV_HS_FOLD_TUNE", 0, 7, ft);
@@ -540,7 +543,7 @@ int cmtv_sync(cmtv_ctx* ctx) {
 
 // the kernels' diagnostic counters of every usable device, summed
 static void read_diag(cmtv_ctx* ctx) {
-  uint64_t late = 0, late_ps = 0;
+  uint64_t late = 0, late_ps = 0, late_sum = 0;
   for (auto& D : ctx->devs) {
     if (D.failed || !D.d_diag) continue;
     (void)hipSetDevice(D.ordinal);
@@ -548,10 +551,12 @@ static void read_diag(cmtv_ctx* ctx) {
     if (hipMemcpy(w, D.d_diag, sizeof(w), hipMemcpyDeviceToHost) == hipSuccess) {
       late += w[kDiagLateK];
       late_ps += w[kDiagLatePs];
+      late_sum += w[kDiagLateSum];
     }
   }
   ctx->stats.late_k_waves = late;
   ctx->stats.late_ps_waves = late_ps;
+  ctx->late_sum_waves = late_sum;
 }
 
 int cmtv_stats_get(cmtv_ctx* ctx, cmtv_stats* out) {
@@ -563,6 +568,16 @@ int cmtv_stats_get(cmtv_ctx* ctx, cmtv_stats* out) {
   ctx->stats.cache_entries = ctx->cache.size();
   ctx->stats.live_devices = (uint32_t)ctx->live.size();
   *out = ctx->stats;
+  return CMTV_OK;
+}
+
+int cmtv_late_sum_waves(cmtv_ctx* ctx, uint64_t* out) {
+  if (!ctx || !out) return CMTV_EINVAL;
+  std::lock_guard<std::mutex> g(ctx->mu);
+  harvest(ctx, true);
+  read_diag(ctx);
+  (void)hipSetDevice(ctx->devs[0].ordinal);
+  *out = ctx->late_sum_waves;
   return CMTV_OK;
 }
 

@@ -437,6 +437,14 @@ struct cmtv_ctx {
   // (CMTV_FORCE_PS_LATE=1: 0, every quad wave does)
   bool hs_fold = true;
   uint32_t ps_wait = cmtv::kPsWaitDefault;
+  // CMTV_HS_SUM_SPLIT=1: that kernel's hash helper and comb wave share every
+  // window's sum (off by default: measured a tie);
+  // CMTV_FORCE_FG_LATE=1: the comb wave's half never arrives and the helper
+  // falls back on every window (it turns the split on unless the other knob
+  // says 0)
+  bool hs_sum_split = false, fg_late = false;
+  // diag[kDiagLateSum] of every device, summed by read_diag (cmtv_late_sum_waves)
+  uint64_t late_sum_waves = 0;
   size_t lane_chunk = cmtv::kChunk;         // signatures per lane-kernel launch (env CMTV_LANE_CHUNK)
   size_t shard_min = cmtv::kShardMinDefault;
   int sr_nops = 0;

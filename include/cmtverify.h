@@ -164,7 +164,11 @@ typedef struct cmtv_device_stats {
  * keyed split kernel's quads never wait for the hash helper and hash their
  * signatures themselves), CMTV_FORCE_PS_LATE=1 (test knob: the Ed25519 quad
  * kernel's quads never wait for the comb wave's [s]B and add the comb rows
- * themselves), CMTV_HS_FOLD=0 (the Ed25519 quad kernel keeps [u]B as a term of
+ * themselves), CMTV_HS_SUM_SPLIT=1 (that kernel's hash helper shares every
+ * window sum with the comb wave instead of forming it alone; off by default),
+ * CMTV_FORCE_FG_LATE=1 (test knob: that split with the comb wave's half
+ * never arriving, so the hash helper forms every sum alone on its fallback
+ * path, counted by cmtv_late_sum_waves), CMTV_HS_FOLD=0 (the Ed25519 quad kernel keeps [u]B as a term of
  * its windows: k_verify_quad_hs instead of k_verify_quad_hs_fold),
  * CMTV_RCCL_LIB=path (the RCCL library to dlopen
  * instead of the system librccl; with CMTV_FORCE_RCCL a repeated ordinal then
@@ -213,6 +217,12 @@ void cmtv_close(cmtv_ctx* ctx);
 const char* cmtv_strerror(int code);
 int cmtv_abi_version(void);
 int cmtv_stats_get(cmtv_ctx* ctx, cmtv_stats* out);
+/* Workgroups of the Ed25519 quad kernel whose hash helper stopped waiting for
+ * the comb wave's half of a window sum and formed the sum alone
+ * (CMTV_HS_SUM_SPLIT=1; CMTV_FORCE_FG_LATE=1 forces it), one count per
+ * workgroup and launch, summed over the context's devices: timing only, never
+ * a verdict. A call of its own, so that cmtv_stats keeps its layout. */
+int cmtv_late_sum_waves(cmtv_ctx* ctx, uint64_t* out);
 /* Stats of the context's g-th device (0 <= g < cmtv_device_count). */
 int cmtv_device_stats_get(cmtv_ctx* ctx, int g, cmtv_device_stats* out);
 /* hipStream_t of the context (as void*), for callers that order their own

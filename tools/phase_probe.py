@@ -20,9 +20,11 @@ which of them waits, and for how long.
 --fold: the five-wave folded kernel's stamps (kernels.hip): per wave 0 entry,
 6 HW_ID, 1 / 2 before / after barrier 1; the comb wave (4) 3 = its share of
 [s]B published; the hash helper 3 = its last sum, 7 = cycles at the window
-barriers; the quads 3 = cycles at the flag, 4 = P_s taken, 5 = exit, 7 as
+barriers, 4 = cycles at its polls for the comb wave's F and G (the split
+window sums); the quads 3 = cycles at the flag, 4 = P_s taken, 5 = exit, 7 as
 the helper. Printed: barrier 1 per role, the comb wave's finish, the quads'
-wait at the flag, the loop length, and which wave shares the comb wave's SIMD.
+wait at the flag, the loop length, the waits at the window barriers and at the
+F/G poll, and which wave shares the comb wave's SIMD.
 """
 import ctypes
 import json
@@ -44,6 +46,7 @@ def fold_report(st, helper_wave):
     cu = (st[:, :, 6] >> 8) & 15
     shares = [int(((simd[:, w] == simd[:, 4]) & (cu[:, w] == cu[:, 4])).sum()) for w in range(4)]
     flag_wait, win_wait = st[:, :, 3].copy(), st[:, :, 7].copy()
+    fg_wait = st[:, helper_wave, 4].copy()  # cycles, not a stamp (0 from a library without the split sums)
     t0 = st[:, :, 0].min(axis=1)
     st = st - t0[:, None, None]
     q, h, c = st[:, quads, :], st[:, helper_wave, :], st[:, 4, :]
@@ -58,6 +61,7 @@ def fold_report(st, helper_wave):
         "quad_flag_wait_median": float(np.median(flag_wait[:, quads])), "quad_flag_wait_max": int(flag_wait[:, quads].max()),
         "b1_release_median": float(np.median(rel)), "loop_median": float(np.median(end - rel)),
         "helper_window_wait_median": float(np.median(win_wait[:, helper_wave])),
+        "helper_fg_wait_median": float(np.median(fg_wait)), "helper_fg_wait_max": int(fg_wait.max()),
         "quad_window_wait_median": float(np.median(win_wait[:, quads])),
         "waves_sharing_comb_simd": {"wave%d" % w: shares[w] for w in range(4)}, "workgroups": int(st.shape[0]),
         "median_wg": {"index": med, "helper_at_b1": int(h[med, 1]), "quads_at_b1": [int(x) for x in q[med, :, 1]],
