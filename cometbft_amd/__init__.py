@@ -10,8 +10,9 @@ from . import _native
 from .crypto import (MODE_GO_STDLIB, MODE_ZIP215, BatchVerifier, Context, KeySet, PubKey, Secp256k1BatchVerifier,
                      Secp256k1KeySet, Secp256k1PubKey, Sr25519BatchVerifier, Sr25519PubKey, default_context, new_batch_verifier,
                      pack_messages)
-from .types import commit_hashes, merkle_root, merkle_roots, valset_hashes
+from .types import Header, commit_hashes, header_hashes, merkle_root, merkle_roots, txs_hash, txs_hashes, valset_hashes
 
-__all__ = ["commit_hashes", "merkle_root", "merkle_roots", "valset_hashes","MODE_GO_STDLIB", "MODE_ZIP215", "BatchVerifier", "Context", "KeySet", "PubKey", "Secp256k1BatchVerifier",
+__all__ = ["Header", "commit_hashes", "header_hashes", "merkle_root", "merkle_roots", "txs_hash", "txs_hashes",
+           "valset_hashes", "MODE_GO_STDLIB", "MODE_ZIP215", "BatchVerifier", "Context", "KeySet", "PubKey", "Secp256k1BatchVerifier",
            "Secp256k1KeySet", "Secp256k1PubKey", "Sr25519BatchVerifier", "Sr25519PubKey", "default_context", "new_batch_verifier",
            "pack_messages", "_native"]

@@ -60,6 +60,7 @@ EXPORTS = (
     "cmtv_alloc_pinned", "cmtv_free_pinned",
     "cmtv_merkle_root", "cmtv_merkle_roots", "cmtv_valset_hash", "cmtv_valset_hashes", "cmtv_commit_hash",
     "cmtv_commit_hashes", "cmtv_validator_bytes", "cmtv_commit_sig_bytes",
+    "cmtv_txs_hash", "cmtv_txs_hashes", "cmtv_header_hash", "cmtv_header_hashes", "cmtv_header_leaf_bytes",
 )
 
 
@@ -110,6 +111,17 @@ class cmtv_commit(ctypes.Structure):
                 ("n_sigs", ctypes.c_uint32), ("flags", _u8p), ("ts_seconds", ctypes.POINTER(ctypes.c_int64)),
                 ("ts_nanos", ctypes.POINTER(ctypes.c_int32)), ("sigs", _u8p),
                 ("sig_off", ctypes.POINTER(ctypes.c_uint32)), ("val_addrs", _u8p)]
+
+
+HDR_LAST_COMMIT_HASH, HDR_DATA_HASH, HDR_VALIDATORS_HASH, HDR_NEXT_VALIDATORS_HASH, HDR_CONSENSUS_HASH, \
+    HDR_APP_HASH, HDR_LAST_RESULTS_HASH, HDR_EVIDENCE_HASH, HDR_PROPOSER_ADDRESS, HDR_N_BYTES_FIELDS = range(10)
+
+
+class cmtv_header(ctypes.Structure):
+    _fields_ = [("version_block", ctypes.c_uint64), ("version_app", ctypes.c_uint64), ("chain_id", ctypes.c_char_p),
+                ("chain_id_len", ctypes.c_uint32), ("height", ctypes.c_int64), ("time_seconds", ctypes.c_int64),
+                ("time_nanos", ctypes.c_int32), ("last_block_id", cmtv_block_id),
+                ("field", _u8p * HDR_N_BYTES_FIELDS), ("field_len", ctypes.c_uint32 * HDR_N_BYTES_FIELDS)]
 
 
 class cmtv_valset(ctypes.Structure):
@@ -267,6 +279,16 @@ def lib() -> ctypes.CDLL:
     L.cmtv_validator_bytes.restype = ctypes.c_int
     L.cmtv_commit_sig_bytes.argtypes = [u32, _u8p, i64, i32, _u8p, sz, _u8p, sz]
     L.cmtv_commit_sig_bytes.restype = ctypes.c_int
+    L.cmtv_txs_hash.argtypes = [vp, sz, _u8p, u32p, _u8p]
+    L.cmtv_txs_hash.restype = ctypes.c_int
+    L.cmtv_txs_hashes.argtypes = [vp, sz, u32p, _u8p, u32p, _u8p]
+    L.cmtv_txs_hashes.restype = ctypes.c_int
+    L.cmtv_header_hash.argtypes = [vp, ctypes.POINTER(cmtv_header), _u8p, _u8p]
+    L.cmtv_header_hash.restype = ctypes.c_int
+    L.cmtv_header_hashes.argtypes = [vp, sz, ctypes.POINTER(cmtv_header), _u8p, _u8p]
+    L.cmtv_header_hashes.restype = ctypes.c_int
+    L.cmtv_header_leaf_bytes.argtypes = [ctypes.POINTER(cmtv_header), u32, _u8p, sz]
+    L.cmtv_header_leaf_bytes.restype = i64
     _lib = L
     return L
 

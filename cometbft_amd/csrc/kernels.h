@@ -1,6 +1,6 @@
 // kernels.h -- host-side launchers for the gfx950 kernels (kernels.hip,
 // keyed_forms.hip, keyed_lane.hip, keygen.hip, sr25519.hip, secp256k1.hip,
-// signbytes.hip, merkle.hip).
+// signbytes.hip, merkle.hip, header.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -200,7 +200,17 @@ hipError_t launch_sign(uint32_t n, const void* seeds, const void* key_idx, const
 //   kMerkleCommitSigs flag u8[g], seconds i64[g], nanos i32[g], address
 //                     addr[20 g ..), signature var[off[g] .. off[g + 1])
 //   kMerkleNodes      node g of `nodes`, the previous pass's output
-enum MerkleLeafKind { kMerkleItems = 0, kMerkleValidators = 1, kMerkleCommitSigs = 2, kMerkleNodes = 3 };
+//   kMerkleTxs        transaction g = var[off[g] .. off[g + 1]) (Txs.Hash())
+// kMerkleHeaders is no pass of that kernel: a "leaf" is a whole header, hashed
+// to its root by launch_header_hash below.
+enum MerkleLeafKind {
+  kMerkleItems = 0,
+  kMerkleValidators = 1,
+  kMerkleCommitSigs = 2,
+  kMerkleNodes = 3,
+  kMerkleTxs = 4,
+  kMerkleHeaders = 5
+};
 struct MerkleLeaves {
   const uint8_t* var = nullptr;
   const uint32_t* off = nullptr;
@@ -213,5 +223,14 @@ struct MerkleLeaves {
 hipError_t launch_merkle_pass(MerkleLeafKind kind, const MerkleLeaves& leaves, const uint32_t* wg_off,
                               const uint32_t* leaf_off, uint32_t n_trees, uint32_t n_wg, uint32_t* out,
                               hipStream_t s);
+
+// Header.Hash() of n headers (header.hip, header.h): root h into out[8 h ..).
+// The fields, header h of n (the constants are header.h's):
+//   off[12 h + f]  where byte field f starts in var (12 n + 1 offsets): the
+//                  chain id, LastBlockID's hash and part-set hash, the nine
+//                  hashes and the proposer address in struct order
+//   i64[k n + h]   version.block, version.app, height, seconds (k = 0..3)
+//   i32[k n + h]   nanos, LastBlockID's part-set total (k = 0, 1)
+hipError_t launch_header_hash(const MerkleLeaves& fields, uint32_t n, uint32_t* out, hipStream_t s);
 
 }  // namespace cmtv

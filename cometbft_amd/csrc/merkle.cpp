@@ -1,21 +1,17 @@
 // merkle.cpp -- the host layer of the merkle engine (merkle.h, merkle.hip):
 // the C ABI's cmtv_merkle_root[s], cmtv_valset_hash[es], cmtv_commit_hash[es]
-// and the two host leaf encoders. A call's trees are cut into runs of about
+// and the two host leaf encoders (header.cpp's calls run through the same
+// engine: merkle_internal.h). A call's trees are cut into runs of about
 // kRunBytes staged bytes; a run is one pinned staging block (the pass prefix
 // arrays and the leaves' struct-of-arrays fields, no encoded leaf), one copy
 // to the context's first device, one launch per pass on its stream and the
 // run's roots back. Two staging slots: the host packs a run while the device
 // hashes the one before.
-#include "runtime_state.h"
+#include "merkle_internal.h"
 // (after hip_runtime.h, which defines CMTV_HD's attributes for a host compile)
-#include "merkle.h"
+#include "header.h"
 
 namespace cmtv {
-namespace {
-
-// staged bytes of a run (a tree is never split: a larger one is a run of its own)
-constexpr uint64_t kRunBytes = 32ull << 20;
-constexpr size_t kRunTrees = 1u << 20;
 
 // google.protobuf.Timestamp as gogo/protobuf's StdTimeMarshal accepts it
 // (types/timestamp.go validateTimestamp; that library is not part of the
@@ -23,18 +19,11 @@ constexpr size_t kRunTrees = 1u << 20;
 // 0001-01-01T00:00:00Z up to, not including, 10000-01-01T00:00:00Z
 constexpr int64_t kMinSeconds = -62135596800ll, kMaxSeconds = 253402300800ll;
 
-bool timestamp_ok(int64_t sec, int32_t nanos) {
+bool merkle_timestamp_ok(int64_t sec, int32_t nanos) {
   return sec >= kMinSeconds && sec < kMaxSeconds && nanos >= 0 && nanos < 1000000000;
 }
 
-// crypto/encoding/codec.go:20-38 PubKeyToProto knows Ed25519 and secp256k1
-// only (an sr25519 key makes Validator.Bytes() panic, SURVEY F9); no codec
-// yields a key of 0 or of more than 64 bytes
-bool validator_ok(uint32_t key_type, size_t pk_len) {
-  return key_type <= CMTV_KEY_SECP256K1 && pk_len >= 1 && pk_len <= 64;
-}
-
-size_t put_uvarint(uint8_t* p, uint64_t v) {
+size_t merkle_put_uvarint(uint8_t* p, uint64_t v) {
   size_t n = 0;
   while (v >= 0x80) {
     p[n++] = (uint8_t)(v | 0x80);
@@ -42,6 +31,25 @@ size_t put_uvarint(uint8_t* p, uint64_t v) {
   }
   p[n++] = (uint8_t)v;
   return n;
+}
+
+bool merkle_offsets_ok(const uint32_t* off, size_t n) {
+  for (size_t i = 0; i < n; i++)
+    if (off[i + 1] < off[i]) return false;
+  return true;
+}
+
+namespace {
+
+// staged bytes of a run (a tree is never split: a larger one is a run of its own)
+constexpr uint64_t kRunBytes = 32ull << 20;
+constexpr size_t kRunTrees = 1u << 20;
+
+// crypto/encoding/codec.go:20-38 PubKeyToProto knows Ed25519 and secp256k1
+// only (an sr25519 key makes Validator.Bytes() panic, SURVEY F9); no codec
+// yields a key of 0 or of more than 64 bytes
+bool validator_ok(uint32_t key_type, size_t pk_len) {
+  return key_type <= CMTV_KEY_SECP256K1 && pk_len >= 1 && pk_len <= 64;
 }
 
 constexpr size_t kValidatorBytesMax = 2 + 2 + 64 + 11;
@@ -57,7 +65,7 @@ size_t encode_validator(uint8_t* p, uint32_t key_type, const uint8_t* pk, size_t
   n += pk_len;
   if (power != 0) {
     p[n++] = 0x10;
-    n += put_uvarint(p + n, (uint64_t)power);
+    n += merkle_put_uvarint(p + n, (uint64_t)power);
   }
   return n;
 }
@@ -69,7 +77,7 @@ void encode_commit_sig(std::vector<uint8_t>& out, uint32_t flag, const uint8_t* 
   size_t n = 0;
   if (flag != 0) {
     b[n++] = 0x08;
-    n += put_uvarint(b + n, flag);
+    n += merkle_put_uvarint(b + n, flag);
   }
   if (addr20) {
     b[n++] = 0x12;
@@ -81,11 +89,11 @@ void encode_commit_sig(std::vector<uint8_t>& out, uint32_t flag, const uint8_t* 
   size_t tl = 0;
   if (sec != 0) {
     t[tl++] = 0x08;
-    tl += put_uvarint(t + tl, (uint64_t)sec);
+    tl += merkle_put_uvarint(t + tl, (uint64_t)sec);
   }
   if (nanos != 0) {
     t[tl++] = 0x10;
-    tl += put_uvarint(t + tl, (uint64_t)(int64_t)nanos);
+    tl += merkle_put_uvarint(t + tl, (uint64_t)(int64_t)nanos);
   }
   b[n++] = 0x1a;
   b[n++] = (uint8_t)tl;
@@ -93,61 +101,15 @@ void encode_commit_sig(std::vector<uint8_t>& out, uint32_t flag, const uint8_t* 
   n += tl;
   if (sig_len) {
     b[n++] = 0x22;
-    n += put_uvarint(b + n, sig_len);
+    n += merkle_put_uvarint(b + n, sig_len);
   }
   out.insert(out.end(), b, b + n);
   if (sig_len) out.insert(out.end(), sig, sig + sig_len);
 }
 
-// Where a run's arrays sit in its staging block (each 16-byte aligned) and,
-// while it is packed, the host pointers to them
-struct Stage {
-  size_t o_pref = 0, o_i64 = 0, o_off = 0, o_i32 = 0, o_u8 = 0, o_addr = 0, o_var = 0, bytes = 0;
-  uint32_t* off = nullptr;
-  int64_t* i64 = nullptr;
-  int32_t* i32 = nullptr;
-  uint8_t* u8 = nullptr;
-  uint8_t* addr = nullptr;
-  uint8_t* var = nullptr;
-};
-
-// The trees of one call and leaf kind
-struct TreeSource {
-  MerkleLeafKind kind;
-  size_t n_trees = 0;
-  explicit TreeSource(MerkleLeafKind k) : kind(k) {}
-  virtual ~TreeSource() = default;
-  virtual uint32_t leaves(size_t t) const = 0;
-  virtual uint64_t var_bytes(size_t t) const = 0;  // its items, keys or signatures
-  // tree t's leaves into the staging, from leaf leaf0 and byte var0 of var
-  // (off[leaf0 + i] for each of them; the engine writes the run's last offset)
-  virtual void pack(size_t t, uint32_t leaf0, uint32_t var0, const Stage& S) const = 0;
-};
-
 void pack_offsets(uint32_t* dst, const uint32_t* src, uint32_t n, uint32_t var0) {
   for (uint32_t i = 0; i < n; i++) dst[i] = var0 + (src[i] - src[0]);
 }
-
-struct ItemTrees : TreeSource {
-  const uint32_t* tree_off;
-  const uint8_t* items;
-  const uint32_t* item_off;
-  ItemTrees(size_t n, const uint32_t* to, const uint8_t* it, const uint32_t* io)
-      : TreeSource(kMerkleItems), tree_off(to), items(it), item_off(io) {
-    n_trees = n;
-  }
-  uint32_t leaves(size_t t) const override { return tree_off[t + 1] - tree_off[t]; }
-  uint64_t var_bytes(size_t t) const override {
-    return leaves(t) ? item_off[tree_off[t + 1]] - item_off[tree_off[t]] : 0u;
-  }
-  void pack(size_t t, uint32_t leaf0, uint32_t var0, const Stage& S) const override {
-    const uint32_t n = leaves(t);
-    if (!n) return;
-    const uint32_t* io = item_off + tree_off[t];
-    pack_offsets(S.off + leaf0, io, n, var0);
-    if (io[n] != io[0]) std::memcpy(S.var + var0, items + io[0], io[n] - io[0]);
-  }
-};
 
 struct ValidatorTrees : TreeSource {
   const cmtv_valset* vals;
@@ -160,7 +122,7 @@ struct ValidatorTrees : TreeSource {
   uint64_t var_bytes(size_t t) const override {
     return vals[t].n_vals ? vals[t].pk_off[vals[t].n_vals] - vals[t].pk_off[0] : 0u;
   }
-  void pack(size_t t, uint32_t leaf0, uint32_t var0, const Stage& S) const override {
+  void pack(size_t t, uint32_t leaf0, uint32_t var0, const MerkleStage& S) const override {
     const cmtv_valset& v = vals[t];
     const uint32_t n = v.n_vals;
     if (!n) return;
@@ -183,7 +145,7 @@ struct CommitTrees : TreeSource {
     const cmtv_commit& c = *commits[t];
     return c.n_sigs ? c.sig_off[c.n_sigs] - c.sig_off[0] : 0u;
   }
-  void pack(size_t t, uint32_t leaf0, uint32_t var0, const Stage& S) const override {
+  void pack(size_t t, uint32_t leaf0, uint32_t var0, const MerkleStage& S) const override {
     const cmtv_commit& c = *commits[t];
     const uint32_t n = c.n_sigs;
     if (!n) return;
@@ -199,8 +161,24 @@ struct CommitTrees : TreeSource {
   }
 };
 
-// per-leaf staged bytes besides the variable ones
-uint64_t leaf_bytes(MerkleLeafKind k) { return k == kMerkleItems ? 4 : k == kMerkleValidators ? 4 + 8 + 1 : 4 + 8 + 4 + 1 + 20; }
+// How many arrays of each type a leaf kind stages per leaf, besides the
+// variable bytes: items and transactions their offset; a validator its power,
+// key offset and key type; a CommitSig its seconds, signature offset, nanos,
+// flag and address; a header (one "leaf" a header: header.h) four 64-bit
+// fields, twelve offsets and two 32-bit fields
+struct LeafArrays {
+  uint32_t i64, off, i32, u8, addr;
+  uint64_t bytes() const { return 8 * i64 + 4 * off + 4 * i32 + u8 + 20 * addr; }
+};
+
+LeafArrays leaf_arrays(MerkleLeafKind k) {
+  switch (k) {
+    case kMerkleValidators: return {1, 1, 0, 1, 0};
+    case kMerkleCommitSigs: return {1, 1, 1, 1, 1};
+    case kMerkleHeaders: return {kHeaderU64Fields, kHeaderVarFields, kHeaderU32Fields, 0, 0};
+    default: return {0, 1, 0, 0, 0};
+  }
+}
 
 // One run, trees [a, b) of S, enqueued on D.stream through staging slot M;
 // its roots arrive in M.h_out (digest words) when M.done has passed.
@@ -223,21 +201,24 @@ int enqueue_run(cmtv_ctx* ctx, CmtvDev& D, MerkleSlot& M, const TreeSource& S, s
     for (size_t t = 0; t < nt; t++) q[t + 1] = q[t] + merkle_blocks(p[t + 1] - p[t]);
     pref.push_back(std::move(q));
   } while (pref.back()[nt] != nt);
-  const size_t n_pass = pref.size() - 1;
-  Stage L;
+  // (a header is reduced to its root by the one launch: no prefix arrays staged)
+  const bool headers = S.kind == kMerkleHeaders;
+  const size_t n_pass = pref.size() - 1, n_pref = headers ? 0 : pref.size();
+  const LeafArrays A = leaf_arrays(S.kind);
+  MerkleStage L;
+  L.n = nl;
   size_t o = 0;
   auto take = [&](size_t bytes) {
     const size_t at = o;
     o = align_up(o + bytes, 16);
     return at;
   };
-  L.o_pref = take(4 * (nt + 1) * pref.size());
-  const bool typed = S.kind != kMerkleItems, commit = S.kind == kMerkleCommitSigs;
-  L.o_i64 = take(typed ? 8 * nl : 0);
-  L.o_off = take(4 * (nl + 1));
-  L.o_i32 = take(commit ? 4 * nl : 0);
-  L.o_u8 = take(typed ? nl : 0);
-  L.o_addr = take(commit ? 20 * nl : 0);
+  L.o_pref = take(4 * (nt + 1) * n_pref);
+  L.o_i64 = take(8 * nl * A.i64);
+  L.o_off = take(4 * (nl * A.off + 1));
+  L.o_i32 = take(4 * nl * A.i32);
+  L.o_u8 = take(nl * A.u8);
+  L.o_addr = take(20 * nl * A.addr);
   // + 4: the aligned reads of the last item end inside its last byte's word
   L.o_var = take(vb + 4);
   L.bytes = o;
@@ -249,7 +230,7 @@ int enqueue_run(cmtv_ctx* ctx, CmtvDev& D, MerkleSlot& M, const TreeSource& S, s
   if ((e = M.h_out.ensure(32 * nt)) != hipSuccess) return hip_fail(e);
   if (!M.done && (e = hipEventCreateWithFlags(&M.done, hipEventDisableTiming)) != hipSuccess) return hip_fail(e);
   auto* h = static_cast<uint8_t*>(M.h_in.p);
-  for (size_t p = 0; p < pref.size(); p++) std::memcpy(h + L.o_pref + 4 * (nt + 1) * p, pref[p].data(), 4 * (nt + 1));
+  for (size_t p = 0; p < n_pref; p++) std::memcpy(h + L.o_pref + 4 * (nt + 1) * p, pref[p].data(), 4 * (nt + 1));
   L.i64 = reinterpret_cast<int64_t*>(h + L.o_i64);
   L.off = reinterpret_cast<uint32_t*>(h + L.o_off);
   L.i32 = reinterpret_cast<int32_t*>(h + L.o_i32);
@@ -261,7 +242,7 @@ int enqueue_run(cmtv_ctx* ctx, CmtvDev& D, MerkleSlot& M, const TreeSource& S, s
     S.pack(a + t, pref[0][t], var0, L);
     var0 += (uint32_t)S.var_bytes(a + t);
   }
-  L.off[nl] = var0;
+  L.off[nl * A.off] = var0;
   std::memset(L.var + vb, 0, 4);
   auto* d = static_cast<uint8_t*>(M.d_in.p);
   hipStream_t s = D.stream;
@@ -284,10 +265,13 @@ int enqueue_run(cmtv_ctx* ctx, CmtvDev& D, MerkleSlot& M, const TreeSource& S, s
     // (the passes' node counts never grow, so both fit)
     out = (p & 1) ? nodes + 8 * w0 : nodes;
     const auto* d_pref = reinterpret_cast<const uint32_t*>(d + L.o_pref);
-    e = (fault_hit(ctx) || D.inject_fault)
-            ? hipErrorLaunchFailure
-            : launch_merkle_pass(p ? kMerkleNodes : S.kind, leaves, d_pref + (nt + 1) * (p + 1),
-                                 d_pref + (nt + 1) * p, (uint32_t)nt, pref[p + 1][nt], out, s);
+    if (fault_hit(ctx) || D.inject_fault)
+      e = hipErrorLaunchFailure;
+    else if (headers)
+      e = launch_header_hash(leaves, (uint32_t)nt, out, s);
+    else
+      e = launch_merkle_pass(p ? kMerkleNodes : S.kind, leaves, d_pref + (nt + 1) * (p + 1), d_pref + (nt + 1) * p,
+                             (uint32_t)nt, pref[p + 1][nt], out, s);
     if (e != hipSuccess) {
       D.timing.abandon(tp);
       return hip_fail(e);
@@ -324,7 +308,7 @@ int merkle_roots_locked(cmtv_ctx* ctx, const TreeSource& S, uint8_t* roots) {
     }
     return CMTV_OK;
   };
-  const uint64_t per_leaf = leaf_bytes(S.kind);
+  const uint64_t per_leaf = leaf_arrays(S.kind).bytes();
   int rc = CMTV_OK;
   size_t t = 0;
   for (int k = 0; t < S.n_trees && rc == CMTV_OK; k ^= 1) {
@@ -348,6 +332,27 @@ int merkle_roots_locked(cmtv_ctx* ctx, const TreeSource& S, uint8_t* roots) {
   return rc;
 }
 
+}  // namespace
+
+void ItemTrees::pack(size_t t, uint32_t leaf0, uint32_t var0, const MerkleStage& S) const {
+  const uint32_t n = leaves(t);
+  if (!n) return;
+  const uint32_t* io = item_off + tree_off[t];
+  pack_offsets(S.off + leaf0, io, n, var0);
+  if (io[n] != io[0]) std::memcpy(S.var + var0, items + io[0], io[n] - io[0]);
+}
+
+bool merkle_item_trees_ok(size_t n_trees, const uint32_t* tree_off, const uint8_t* items, const uint32_t* item_off,
+                          const uint8_t* out) {
+  if (!tree_off || !out || !merkle_offsets_ok(tree_off, n_trees)) return false;
+  const uint32_t first = tree_off[0], last = tree_off[n_trees];
+  if (last != first) {
+    if (!item_off || !merkle_offsets_ok(item_off + first, last - first)) return false;
+    if (!items && item_off[last] != item_off[first]) return false;
+  }
+  return true;
+}
+
 // A call: the context lock, the first device, the roots into a buffer of the
 // call's own and into out only when all of them are there.
 int merkle_call(cmtv_ctx* ctx, const TreeSource& S, uint8_t* out) {
@@ -363,11 +368,7 @@ int merkle_call(cmtv_ctx* ctx, const TreeSource& S, uint8_t* out) {
   return CMTV_OK;
 }
 
-bool offsets_ok(const uint32_t* off, size_t n) {
-  for (size_t i = 0; i < n; i++)
-    if (off[i + 1] < off[i]) return false;
-  return true;
-}
+namespace {
 
 bool valset_ok(const cmtv_valset& v, const uint8_t* kt) {
   if (v.n_vals == 0) return true;
@@ -384,10 +385,10 @@ bool commit_ok(const cmtv_commit& c, bool* wide) {
   *wide = false;
   if (c.n_sigs == 0) return true;
   if (!c.flags || !c.ts_seconds || !c.ts_nanos || !c.sig_off) return false;
-  if (!offsets_ok(c.sig_off, c.n_sigs)) return false;
+  if (!merkle_offsets_ok(c.sig_off, c.n_sigs)) return false;
   if (!c.sigs && c.sig_off[c.n_sigs] != c.sig_off[0]) return false;
   for (uint32_t i = 0; i < c.n_sigs; i++) {
-    if (!timestamp_ok(c.ts_seconds[i], c.ts_nanos[i])) return false;
+    if (!merkle_timestamp_ok(c.ts_seconds[i], c.ts_nanos[i])) return false;
     if (!c.val_addrs && c.flags[i] != kMerkleFlagAbsent) return false;
     if (c.sig_off[i + 1] - c.sig_off[i] > 64) *wide = true;
   }
@@ -405,19 +406,28 @@ int cmtv_merkle_roots(cmtv_ctx* ctx, size_t n_trees, const uint32_t* tree_off, c
                       const uint32_t* item_off, uint8_t* out) {
   if (!ctx || n_trees > (1ull << 31)) return CMTV_EINVAL;
   if (n_trees == 0) return CMTV_OK;
-  if (!tree_off || !out || !offsets_ok(tree_off, n_trees)) return CMTV_EINVAL;
-  const uint32_t first = tree_off[0], last = tree_off[n_trees];
-  if (last != first) {
-    if (!item_off || !offsets_ok(item_off + first, last - first)) return CMTV_EINVAL;
-    if (!items && item_off[last] != item_off[first]) return CMTV_EINVAL;
-  }
-  return merkle_call(ctx, ItemTrees(n_trees, tree_off, items, item_off), out);
+  if (!merkle_item_trees_ok(n_trees, tree_off, items, item_off, out)) return CMTV_EINVAL;
+  return merkle_call(ctx, ItemTrees(kMerkleItems, n_trees, tree_off, items, item_off), out);
 }
 
 int cmtv_merkle_root(cmtv_ctx* ctx, size_t n, const uint8_t* items, const uint32_t* item_off, uint8_t out[32]) {
   if (n > 0xFFFFFFFFull) return CMTV_EINVAL;
   const uint32_t tree_off[2] = {0u, (uint32_t)n};
   return cmtv_merkle_roots(ctx, 1, tree_off, items, item_off, out);
+}
+
+int cmtv_txs_hashes(cmtv_ctx* ctx, size_t n_blocks, const uint32_t* block_off, const uint8_t* txs,
+                    const uint32_t* tx_off, uint8_t* out) {
+  if (!ctx || n_blocks > (1ull << 31)) return CMTV_EINVAL;
+  if (n_blocks == 0) return CMTV_OK;
+  if (!merkle_item_trees_ok(n_blocks, block_off, txs, tx_off, out)) return CMTV_EINVAL;
+  return merkle_call(ctx, ItemTrees(kMerkleTxs, n_blocks, block_off, txs, tx_off), out);
+}
+
+int cmtv_txs_hash(cmtv_ctx* ctx, size_t n, const uint8_t* txs, const uint32_t* tx_off, uint8_t out[32]) {
+  if (n > 0xFFFFFFFFull) return CMTV_EINVAL;
+  const uint32_t block_off[2] = {0u, (uint32_t)n};
+  return cmtv_txs_hashes(ctx, 1, block_off, txs, tx_off, out);
 }
 
 int cmtv_valset_hashes(cmtv_ctx* ctx, size_t n, const cmtv_valset* vals, const uint8_t* const* key_types,
@@ -470,7 +480,7 @@ int cmtv_commit_hashes(cmtv_ctx* ctx, size_t n, const cmtv_commit* commits, uint
     if ((rc = merkle_call(ctx, dev, part.data())) != CMTV_OK) return rc;
     for (size_t k = 0; k < dev_at.size(); k++) std::memcpy(&roots[32 * dev_at[k]], &part[32 * k], 32);
   }
-  rc = merkle_call(ctx, ItemTrees(wide_at.size(), tree_off.data(), items.data(), item_off.data()), part.data());
+  rc = merkle_call(ctx, ItemTrees(kMerkleItems, wide_at.size(), tree_off.data(), items.data(), item_off.data()), part.data());
   if (rc != CMTV_OK) return rc;
   for (size_t k = 0; k < wide_at.size(); k++) std::memcpy(&roots[32 * wide_at[k]], &part[32 * k], 32);
   std::memcpy(out, roots.data(), roots.size());
@@ -492,7 +502,7 @@ int cmtv_validator_bytes(uint32_t key_type, const uint8_t* pk, size_t pk_len, in
 
 int cmtv_commit_sig_bytes(uint32_t flag, const uint8_t* addr20_or_null, int64_t ts_seconds, int32_t ts_nanos,
                           const uint8_t* sig, size_t sig_len, uint8_t* out, size_t cap) {
-  if ((!sig && sig_len) || (!out && cap) || sig_len > (1u << 30) || !timestamp_ok(ts_seconds, ts_nanos))
+  if ((!sig && sig_len) || (!out && cap) || sig_len > (1u << 30) || !merkle_timestamp_ok(ts_seconds, ts_nanos))
     return CMTV_EINVAL;
   std::vector<uint8_t> b;
   encode_commit_sig(b, flag, addr20_or_null, ts_seconds, ts_nanos, sig, sig_len);

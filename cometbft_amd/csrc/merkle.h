@@ -283,6 +283,23 @@ CMTV_HD void merkle_leaf_hash(uint32_t out[8], const uint8_t* item, uint32_t len
   }
 }
 
+// The leaf of a transaction in Txs.Hash() (types/tx.go:29-31, 47-55):
+// SHA-256(0x00 || SHA-256(tx)), the transaction anywhere in global memory and
+// of any length (sha256_msg's block loop), then the 33-byte leaf in one block
+CMTV_HD void merkle_tx_leaf_hash(uint32_t out[8], const uint8_t* tx, uint32_t len) {
+  uint32_t d[8], w[16];
+  sha256_msg(d, tx, len);
+  w[0] = d[0] >> 8;
+#pragma unroll
+  for (int k = 1; k < 8; k++) w[k] = funnel_bytes(d[k - 1], d[k], 1);
+  w[8] = (d[7] << 24) | 0x00800000u;
+#pragma unroll
+  for (int k = 9; k < 15; k++) w[k] = 0u;
+  w[15] = 8 * 33;
+  sha256_init(out);
+  sha256_compress(out, w);
+}
+
 // SHA-256(0x01 || left || right), n = the two nodes' sixteen digest words. The
 // 65-byte message sits one byte off the words: block 1 is sixteen funnel
 // shifts, block 2 the last byte, the padding and the length 520.

@@ -1,7 +1,8 @@
 // merkle.hip -- k_merkle_pass: RFC 6962 merkle roots of many trees per launch
 // (merkle.h; crypto/merkle/tree.go:9, types/validator_set.go:347 Hash,
 // types/block.go:894 Commit.Hash). One lane hashes one leaf -- an item in
-// global memory, a validator or a CommitSig encoded in registers from the
+// global memory, a transaction (Txs.Hash(): hashed, then hashed as an item), a
+// validator or a CommitSig encoded in registers from the
 // struct-of-arrays fields, or a node of the previous pass -- and the
 // workgroup reduces its aligned block of kMerkleB leaves to one node in LDS,
 // one barrier per level, two word-planar level buffers (16 KiB).
@@ -22,6 +23,14 @@ struct ItemLeaf {
   __device__ __forceinline__ void operator()(uint32_t g, uint32_t h[8]) const {
     const uint32_t o = a.off[g];
     merkle_leaf_hash(h, a.var + o, a.off[g + 1] - o);
+  }
+};
+
+struct TxLeaf {
+  MerkleLeaves a;
+  __device__ __forceinline__ void operator()(uint32_t g, uint32_t h[8]) const {
+    const uint32_t o = a.off[g];
+    merkle_tx_leaf_hash(h, a.var + o, a.off[g + 1] - o);
   }
 };
 
@@ -111,6 +120,9 @@ hipError_t launch_merkle_pass(MerkleLeafKind kind, const MerkleLeaves& leaves, c
     case kMerkleCommitSigs:
       hipLaunchKernelGGL(k_merkle_pass<CommitSigLeaf>, grid, block, 0, s, CommitSigLeaf{leaves}, wg_off, leaf_off,
                          n_trees, out);
+      break;
+    case kMerkleTxs:
+      hipLaunchKernelGGL(k_merkle_pass<TxLeaf>, grid, block, 0, s, TxLeaf{leaves}, wg_off, leaf_off, n_trees, out);
       break;
     case kMerkleNodes:
       hipLaunchKernelGGL(k_merkle_pass<NodeLeaf>, grid, block, 0, s, NodeLeaf{leaves}, wg_off, leaf_off, n_trees, out);

@@ -1,7 +1,7 @@
 // runtime_state.h -- the state of a context and its devices, the constants of
 // the verification forms and the small helpers every launch path inlines.
 // Private to the runtime's own files (runtime.cpp, launch.cpp, host_batch.cpp,
-// gather.cpp, keyset.cpp, bulk_lane.cpp, merkle.cpp): the commit and pipeline layers see
+// gather.cpp, keyset.cpp, bulk_lane.cpp, merkle.cpp, header.cpp): the commit and pipeline layers see
 // runtime_internal.h only.
 #pragma once
 #include <hip/hip_runtime.h>

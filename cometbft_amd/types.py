@@ -375,6 +375,101 @@ def commit_hashes(commits, ctx: Context | None = None) -> list:
     return _roots(out, len(commits))
 
 
+@dataclass
+class Header:
+    """types/block.go Header, the fields Hash() reads, in struct order."""
+    version_block: int = 0
+    version_app: int = 0
+    chain_id: str = ""
+    height: int = 0
+    time: tuple = (GO_ZERO_TIME_SECONDS, 0)  # (unix seconds, nanos)
+    last_block_id: BlockID = field(default_factory=BlockID)
+    last_commit_hash: bytes = b""
+    data_hash: bytes = b""
+    validators_hash: bytes = b""
+    next_validators_hash: bytes = b""
+    consensus_hash: bytes = b""
+    app_hash: bytes = b""
+    last_results_hash: bytes = b""
+    evidence_hash: bytes = b""
+    proposer_address: bytes = b""
+
+    def _bytes_fields(self) -> tuple:
+        """The nine byte fields in CMTV_HDR_* order."""
+        return (self.last_commit_hash, self.data_hash, self.validators_hash, self.next_validators_hash,
+                self.consensus_hash, self.app_hash, self.last_results_hash, self.evidence_hash, self.proposer_address)
+
+    def _c(self):
+        cid = self.chain_id.encode()
+        bid, keep = self.last_block_id._c()
+        h = N.cmtv_header(version_block=self.version_block, version_app=self.version_app, chain_id=cid,
+                          chain_id_len=len(cid), height=self.height, time_seconds=self.time[0],
+                          time_nanos=self.time[1], last_block_id=bid)
+        bufs = []
+        for i, b in enumerate(self._bytes_fields()):
+            buf = (ctypes.c_uint8 * max(len(b), 1)).from_buffer_copy(b + b"\0")
+            h.field[i] = ctypes.cast(buf, ctypes.POINTER(ctypes.c_uint8))
+            h.field_len[i] = len(b)
+            bufs.append(buf)
+        return h, (cid, keep, bufs)
+
+    def hash(self, ctx: Context | None = None) -> Optional[bytes]:
+        """Header.Hash() (types/block.go:440) on the device (cmtv_header_hash);
+        None where the reference returns nil."""
+        return header_hashes([self], ctx)[0]
+
+
+def header_hashes(headers, ctx: Context | None = None) -> list:
+    """Header.Hash() of every header in one cmtv_header_hashes call; None for a
+    header without a hash."""
+    ctx = ctx or default_context()
+    headers = list(headers)
+    if not headers:
+        return []
+    arr = (N.cmtv_header * len(headers))()
+    keep = []
+    for i, h in enumerate(headers):
+        arr[i], kh = h._c()
+        keep.append(kh)
+    out = (ctypes.c_uint8 * (32 * len(headers)))()
+    has = (ctypes.c_uint8 * len(headers))()
+    N.check(N.lib().cmtv_header_hashes(ctx.handle, len(headers), arr, out, has), "cmtv_header_hashes")
+    return [r if ok else None for r, ok in zip(_roots(out, len(headers)), has)]
+
+
+def txs_hashes(blocks, ctx: Context | None = None) -> list:
+    """Txs.Hash() (types/tx.go:47) of every block's transaction list, a
+    sequence of sequences of byte strings, in one cmtv_txs_hashes call."""
+    ctx = ctx or default_context()
+    blocks = [list(b) for b in blocks]
+    if not blocks:
+        return []
+    txs = [tx for b in blocks for tx in b]
+    block_off = np.zeros(len(blocks) + 1, np.uint32)
+    block_off[1:] = np.cumsum([len(b) for b in blocks])
+    tx_off = np.zeros(len(txs) + 1, np.uint32)
+    if txs:
+        tx_off[1:] = np.cumsum([len(tx) for tx in txs])
+    blob = np.frombuffer(b"".join(txs) + b"\0", np.uint8).copy()
+    out = (ctypes.c_uint8 * (32 * len(blocks)))()
+    N.check(N.lib().cmtv_txs_hashes(ctx.handle, len(blocks), _p32(block_off), _p8(blob), _p32(tx_off), out),
+            "cmtv_txs_hashes")
+    return _roots(out, len(blocks))
+
+
+def txs_hash(txs, ctx: Context | None = None) -> bytes:
+    """Txs.Hash() of one list of transactions (cmtv_txs_hash)."""
+    ctx = ctx or default_context()
+    txs = list(txs)
+    tx_off = np.zeros(len(txs) + 1, np.uint32)
+    if txs:
+        tx_off[1:] = np.cumsum([len(tx) for tx in txs])
+    blob = np.frombuffer(b"".join(txs) + b"\0", np.uint8).copy()
+    out = (ctypes.c_uint8 * 32)()
+    N.check(N.lib().cmtv_txs_hash(ctx.handle, len(txs), _p8(blob), _p32(tx_off), out), "cmtv_txs_hash")
+    return bytes(out)
+
+
 def _verify(vals: ValidatorSet, kind, chain_id, block_id, height, commit, num, den, ctx, mode):
     ctx = ctx or default_context()
     vs, keep_v = vals._pack()

@@ -717,6 +717,66 @@ int cmtv_validator_bytes(uint32_t key_type, const uint8_t* pk, size_t pk_len, in
 int cmtv_commit_sig_bytes(uint32_t flag, const uint8_t* addr20_or_null, int64_t ts_seconds, int32_t ts_nanos,
                           const uint8_t* sig, size_t sig_len, uint8_t* out, size_t cap);
 
+/* Txs.Hash() (types/tx.go:47-55), the DataHash of a block: the root over
+ * SHA-256(tx) of every transaction, so the leaf of a transaction is
+ * SHA-256(0x00 || SHA-256(tx)); an empty list hashes to SHA-256(""). The
+ * arguments and rules are those of cmtv_merkle_root[s], a transaction in the
+ * place of an item, a block's list in the place of a tree. */
+int cmtv_txs_hash(cmtv_ctx* ctx, size_t n, const uint8_t* txs, const uint32_t* tx_off, uint8_t out[32]);
+int cmtv_txs_hashes(cmtv_ctx* ctx, size_t n_blocks, const uint32_t* block_off, const uint8_t* txs,
+                    const uint32_t* tx_off, uint8_t* out);
+
+/* Header.Hash() (types/block.go:440-475): the root over the header's fourteen
+ * fields in struct order, each encoded as the reference does
+ * (Version.Marshal, cdcEncode of the chain id, the height and the ten byte
+ * fields, StdTimeMarshal, BlockID.ToProto().Marshal), the leaves built on the
+ * device from the fields below; one launch hashes every header of a run.
+ * field[] holds the nine byte fields in struct order, CMTV_HDR_*.
+ *
+ * The reference returns nil for a header with an empty ValidatorsHash or a
+ * time that StdTimeMarshal refuses (the bounds of cmtv_commit_hash above):
+ * such a header gets has_hash[i] = 0 and 32 zero bytes and costs no device
+ * work, every other one has_hash[i] = 1. With has_hash NULL a header without
+ * a hash makes the call CMTV_EINVAL. A NULL pointer with a non-zero length is
+ * CMTV_EINVAL; nothing is written to out or has_hash unless the call returns
+ * CMTV_OK.
+ *
+ * A header with a chain id or a byte field of more than 64 bytes, or a
+ * LastBlockID hash of more than 32, has its leaves encoded on the host and
+ * is hashed as a tree of items, with the same root and in its own place in
+ * out; a call may mix both kinds. */
+enum {
+  CMTV_HDR_LAST_COMMIT_HASH = 0,
+  CMTV_HDR_DATA_HASH,
+  CMTV_HDR_VALIDATORS_HASH,
+  CMTV_HDR_NEXT_VALIDATORS_HASH,
+  CMTV_HDR_CONSENSUS_HASH,
+  CMTV_HDR_APP_HASH,
+  CMTV_HDR_LAST_RESULTS_HASH,
+  CMTV_HDR_EVIDENCE_HASH,
+  CMTV_HDR_PROPOSER_ADDRESS,
+  CMTV_HDR_N_BYTES_FIELDS
+};
+typedef struct cmtv_header {
+  uint64_t version_block, version_app; /* version.Consensus */
+  const char* chain_id;
+  uint32_t chain_id_len;
+  int64_t height;
+  int64_t time_seconds;
+  int32_t time_nanos;
+  cmtv_block_id last_block_id;
+  const uint8_t* field[CMTV_HDR_N_BYTES_FIELDS];
+  uint32_t field_len[CMTV_HDR_N_BYTES_FIELDS];
+} cmtv_header;
+int cmtv_header_hash(cmtv_ctx* ctx, const cmtv_header* h, uint8_t out[32], uint8_t* has_hash);
+int cmtv_header_hashes(cmtv_ctx* ctx, size_t n, const cmtv_header* hs, uint8_t* out /* n x 32 */,
+                       uint8_t* has_hash /* n, may be NULL */);
+/* Leaf 0..13 as Header.Hash() encodes it, on the host (no device): the length
+ * or a negative code, the bytes written when they fit cap (as
+ * cmtv_vote_sign_bytes). CMTV_EINVAL: a leaf above 13, a NULL pointer with a
+ * length, leaf 3 of a time that StdTimeMarshal refuses. */
+int64_t cmtv_header_leaf_bytes(const cmtv_header* h, uint32_t leaf, uint8_t* out, size_t cap);
+
 /* ------------------------------------------------------------ test-data generation */
 
 /* RFC 8032 key generation and deterministic signing on the device (the
