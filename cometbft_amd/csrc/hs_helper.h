@@ -130,6 +130,32 @@ __device__ __forceinline__ void hs_helper_sums(const SigPrep& p, int W, const ui
   }
 }
 
+// hs_helper_sums software-pipelined over the two waves of the folded form's
+// helper SIMD (k_verify_quad_hs_fold; quad.h h_sums_pipe): both the hash
+// helper (lead) and the comb wave run this, on the same lanes, digits and
+// table reads, and each forms every second window's sum -- its front half in
+// one interval, its back half and the store to ring slot (win & 1) in the
+// next, the interval in which hs_helper_sums stores it. The window barrier
+// is the only synchronisation; both meet all W - 1. In interval 0 the lead
+// forms all of S_{W-2} while the other wave starts S_{W-3} beside it, and the
+// quads need S_{W-2} after one addition and four doublings: the caller gives
+// the lead the SIMD's issue priority for it, and first_done() after that
+// first barrier takes it back.
+template <class Clock, class FirstDone>
+__device__ __forceinline__ void hs_helper_sums_pipe(const SigPrep& p, int W, const uint2* tabs, uint2* ring,
+                                                    uint32_t t, bool lead, const Clock& clock, uint64_t& hwait,
+                                                    const FirstDone& first_done) {
+  HsWalk rd(p, W, tabs, t);
+  h_sums_pipe(
+      rd, W, lead, [&](int win, const fe* out) { hs_slot_store(ring + (win & 1) * kHsSlotU2, t, out); },
+      [&](int win) {
+        const uint64_t c0 = clock();
+        __syncthreads();  // window win
+        hwait += clock() - c0;
+        if (win == W - 2) first_done();
+      });
+}
+
 // hs_helper_sums split over the two waves of the folded form's helper SIMD
 // (k_verify_quad_hs_fold): the hash helper runs hs_helper_sums_eh and the comb
 // wave hs_helper_sums_fg, on the same lanes, digits and table reads. Per

@@ -38,6 +38,10 @@ constexpr uint32_t kFormMask = 0xFF, kLaunchForceWide = 0x100, kLaunchHsFold = 0
 // split over the hash helper and the comb wave (CMTV_HS_SUM_SPLIT); the comb
 // wave's half never arrives (the CMTV_FORCE_FG_LATE test knob)
 constexpr uint32_t kHsTuneSumSplit = 1u << 11, kHsTuneFgLate = 1u << 12;
+// hs_tune bit 13, the same kernel: the window sums are software-pipelined over
+// those two waves, each sum whole on one wave (CMTV_HS_SUM_PIPE); without
+// effect under kHsTuneSumSplit
+constexpr uint32_t kHsTunePipe = 1u << 13;
 // registered-key forms (launch_verify_keyed): the keyed row kernel
 // (k_verify_keyed_row_split, one signature per workgroup), the keyed quad
 // kernel with two helper waves (k_verify_keyed_quad_split), the lane kernels

@@ -216,7 +216,17 @@ __global__ __launch_bounds__(256, CMTV_QUAD_WAVES_PER_EU) void k_verify_quad_hs(
 // diag[kDiagLateSum] (cmtv_late_sum_waves); kHsTuneFgLate (the
 // CMTV_FORCE_FG_LATE test knob) makes the comb wave idle and every window take
 // that path.
-template <uint32_t MODE>
+//
+// PIPE (the launcher picks it for hs_tune's kHsTunePipe, CMTV_HS_SUM_PIPE,
+// unless kHsTuneSumSplit is set or the helper is on wave 3) keeps every sum
+// whole and pipelines the sums over the two waves instead (hs_helper.h
+// hs_helper_sums_pipe): each forms every second window's sum, half of it per
+// window, and the window barrier stays the only synchronisation -- no flag, no
+// poll, no exchange area, no late path. It is a kernel of its own, so that the
+// other one stays instruction for instruction what it was: a rebuild of this
+// kernel around unrelated code has moved its time by 2% either way (DESIGN.md
+// 5 rounds 9 and 10).
+template <uint32_t MODE, bool PIPE>
 __global__ __launch_bounds__(320, 1) void k_verify_quad_hs_fold(
     uint32_t n, const uint32_t* __restrict__ pk, const uint32_t* __restrict__ sig, const uint8_t* __restrict__ msg,
     const uint32_t* __restrict__ off, const uint32_t* __restrict__ btab, uint8_t* __restrict__ out_valid,
@@ -250,7 +260,8 @@ __global__ __launch_bounds__(320, 1) void k_verify_quad_hs_fold(
   // probe slots: 0 entry, 6 HW_ID; 1 / 2 before / after barrier 1; comb wave
   // 3 = P_s published; helper 3 = its last sum, 7 = cycles at the window
   // barriers, 4 = cycles at its polls for F and G; quads 4 = P_s taken,
-  // 3 = cycles at the flag, 5 = exit, 7 as the helper
+  // 3 = cycles at the flag, 5 = exit, 7 as the helper; PIPE: comb wave 7 as
+  // the helper
   CMTV_STAMP5(0);
   CMTV_HWID5();
   if (threadIdx.x == 0) {
@@ -288,6 +299,15 @@ __global__ __launch_bounds__(320, 1) void k_verify_quad_hs_fold(
     __syncthreads();  // 1
     CMTV_STAMP5(2);
     const int W = (int)__builtin_amdgcn_readfirstlane((prep[0][24] >> 16) & 0xFFu);
+    if constexpr (PIPE) {
+      SigPrep p;
+      sig_prep_load_pair(p, prep[t < 48 ? t : 47]);
+      uint64_t hwait = 0;
+      hs_helper_sums_pipe(
+          p, W, &tab_lds[0][0], xbuf, t, false, [] { return (uint64_t)CMTV_CLOCK(); }, hwait, [] {});
+      CMTV_STAMP5_VAL(7, hwait);
+      return;
+    }
     if (sum_split && !fg_late) {
       SigPrep p;
       sig_prep_load_pair(p, prep[t < 48 ? t : 47]);
@@ -316,7 +336,12 @@ __global__ __launch_bounds__(320, 1) void k_verify_quad_hs_fold(
     uint64_t hwait = 0, fwait = 0;  // probe build: cycles the helper waits at the window barriers, for F and G
     (void)fwait;
     auto clock = [] { return (uint64_t)CMTV_CLOCK(); };
-    if (sum_split) {
+    if constexpr (PIPE) {
+      // S_{W-2} is all this wave's, beside the comb wave's first front half, and
+      // the quads need it after one addition and four doublings
+      __builtin_amdgcn_s_setprio(3);
+      hs_helper_sums_pipe(p, W, &tab_lds[0][0], xbuf, t, true, clock, hwait, [] { CMTV_URGENT(); });
+    } else if (sum_split) {
       const bool late = hs_helper_sums_eh(p, W, &tab_lds[0][0], xbuf, fgx, &fg_ready, fg_late ? 0u : kPsWaitDefault, t,
                                           clock, hwait, fwait);
       if (late && t == 0 && diag) atomicAdd(diag + kDiagLateSum, 1u);
@@ -385,6 +410,11 @@ __global__ __launch_bounds__(320, 1) void k_verify_quad_hs_fold(
   CMTV_STAMP5(5);
   CMTV_STAMP5_VAL(7, qwait);
   quad_verdict_store(v, active, s, n, wave, t, out_valid, out_bitmap, tags);
+}
+
+// whether a launch with these hs_tune bits runs k_verify_quad_hs_fold's PIPE form
+static bool hs_fold_pipe(uint32_t hs_tune) {
+  return (hs_tune & kHsTunePipe) != 0 && (hs_tune & kHsTuneSumSplit) == 0 && ((hs_tune >> 8) & 1u) == 0;
 }
 
 // The oct verifier over two waves per 8 signatures: wave 1 hashes and splits
@@ -712,9 +742,12 @@ hipError_t launch_verify(uint32_t mode, uint32_t n, const void* pk, const void* 
         // 48 signatures per 256-lane block; enough blocks for every 16-bit
         // slice of every bitmap word; of rs, its tagged entries only
         const uint32_t slices = 4 * ((n + 63) / 64);
-        if (kflags & kLaunchHsFold)
-          hipLaunchKernelGGL(k_verify_quad_hs_fold<M>, dim3((slices + 2) / 3), dim3(320), 0, s, n, pkp, sgp, mp, op,
-                             btab, vp, bp, fw, fz, kflags >> 16, ps_wait, diag, rs);
+        if ((kflags & kLaunchHsFold) && hs_fold_pipe(kflags >> 16))
+          hipLaunchKernelGGL((k_verify_quad_hs_fold<M, true>), dim3((slices + 2) / 3), dim3(320), 0, s, n, pkp, sgp, mp,
+                             op, btab, vp, bp, fw, fz, kflags >> 16, ps_wait, diag, rs);
+        else if (kflags & kLaunchHsFold)
+          hipLaunchKernelGGL((k_verify_quad_hs_fold<M, false>), dim3((slices + 2) / 3), dim3(320), 0, s, n, pkp, sgp, mp,
+                             op, btab, vp, bp, fw, fz, kflags >> 16, ps_wait, diag, rs);
         else
           hipLaunchKernelGGL(k_verify_quad_hs<M>, dim3((slices + 2) / 3), dim3(256), 0, s, n, pkp, sgp, mp, op, btab,
                              vp, bp, fw, fz, kflags >> 16, rs);

@@ -116,7 +116,8 @@ int enqueue_verify(cmtv_ctx* ctx, CmtvDev& D, size_t n, const uint8_t* d_pk, con
   const uint32_t form = sr ? sr_form(ctx, n) : ed_form(ctx, n);
   const bool lane = form == kFormLane;
   const bool row = form == kFormRow || form == kFormRow4;
-  const uint32_t hs_tune = ctx->hs_tune | (ctx->hs_sum_split ? kHsTuneSumSplit : 0u) | (ctx->fg_late ? kHsTuneFgLate : 0u);
+  const uint32_t hs_tune = ctx->hs_tune | (ctx->hs_sum_split ? kHsTuneSumSplit : 0u) |
+                           (ctx->fg_late ? kHsTuneFgLate : 0u) | (ctx->hs_sum_pipe ? kHsTunePipe : 0u);
   const uint32_t kflags = form | (form == kFormQuad ? hs_tune << 16 : 0u) |
                           (ctx->force_wide ? kLaunchForceWide : 0u) | (ctx->hs_fold ? kLaunchHsFold : 0u);
   hipError_t e = hipSuccess;

@@ -911,6 +911,104 @@ CMTV_HD void h_window_addend_xy(fe& out0, fe& out1, const fe& e, const fe& f, co
   fe_add(out1, Y3, X3);
 }
 
+// h_window_addend cut in two halves of 5 multiplications each, for two waves
+// that each form every second window's sum and run one half per window
+// (h_sums_pipe below): again the same formulas on the same operands in the
+// same order, so every limb of out[0..3] is h_window_addend's. _front reads
+// the tables (A, B, 2d T2, C, D) and keeps E, F, G, H; _back reads nothing
+// (X3, Y3, Z3, T3, 2d T3).
+template <class Rd>
+CMTV_HD void h_window_addend_front(fe& e, fe& f, fe& g, fe& h, const Rd& rd, int dA, int dR, bool r_flip) {
+  const int eA = dA < 0 ? -dA : dA, eR = dR < 0 ? -dR : dR;
+  const bool nA = dA < 0, nR = (dR < 0) != r_flip;
+  fe x, y, s, d, m, s2, d2;
+  rd(0, eA, 0, x);
+  rd(0, eA, 1, y);
+  fe_sub(d, y, x);  // Y1 - X1
+  fe_add(s, y, x);  // Y1 + X1
+  rd(1, eR, 0, x);
+  rd(1, eR, 1, y);
+  fe_sub(d2, y, x);  // Y2 - X2
+  fe_add(s2, y, x);  // Y2 + X2
+  fe_select(x, d, s, nA);
+  fe_select(m, d2, s2, nR);
+  fe_mul(x, x, m);  // A
+  fe_select(y, s, d, nA);
+  fe_select(m, s2, d2, nR);
+  fe_mul(y, y, m);  // B
+  fe_sub(e, y, x);  // E = B - A
+  fe_add(h, y, x);  // H = B + A
+  rd(1, eR, 3, m);
+  fe_const_d2(d2);
+  fe_mul(m, m, d2);  // 2d T2
+  rd(0, eA, 3, x);
+  fe_mul(x, x, m);  // +/- C = T1 2dT2
+  rd(0, eA, 2, y);
+  rd(1, eR, 2, m);
+  fe_add(m, m, m);
+  fe_mul(y, y, m);  // D = Z1 2Z2
+  fe_add(s, y, x);  // D + C
+  fe_sub(d, y, x);  // D - C
+  const bool cneg = nA != nR;
+  fe_select(f, d, s, cneg);  // F = D - C
+  fe_select(g, s, d, cneg);  // G = D + C
+}
+
+CMTV_HD void h_window_addend_back(fe out[4], const fe& e, const fe& f, const fe& g, const fe& h) {
+  fe X3, Y3, Z3, T3, m;
+  fe_mul(X3, e, f);
+  fe_mul(Y3, g, h);
+  fe_mul(Z3, f, g);
+  fe_mul(T3, e, h);
+  fe_sub(out[0], Y3, X3);
+  fe_add(out[1], Y3, X3);
+  fe_add(out[2], Z3, Z3);
+  fe_const_d2(m);
+  fe_mul(out[3], T3, m);
+}
+
+// The window sums S_{W-2} .. S_0 software-pipelined over two waves that share
+// a SIMD (k_verify_quad_hs_fold's hash helper and comb wave; hs_helper.h
+// hs_helper_sums_pipe): a lone wave issues at half the SIMD's rate, so two
+// waves on independent work finish a sum's 10 products sooner than one wave
+// alone -- and splitting one sum (h_window_addend_eh / _fg) makes them
+// dependent, while two sums in flight do not. Interval i ends at window
+// barrier win = W - 2 - i. Ownership of the sums alternates from the lead
+// wave at S_{W-2}: in interval i the owner of S_win runs the back half and
+// hands the sum to store(win, out) -- the interval in which a lone helper
+// would -- while the other wave runs the front half of S_{win-1}, its own next
+// one, which reads only the tables; the lead forms all of S_{W-2} in interval
+// 0. Then both call barrier(win): W - 1 times each, the only synchronisation.
+// Both walk the same digits (rd.next(dA, dR), one pair per window from W - 2
+// down) and each consumes every second pair.
+CMTV_HD bool h_sums_pipe_owns(int W, int win, bool lead) { return (((W - 2 - win) & 1) == 0) == lead; }
+
+template <class Walk, class Store, class Barrier>
+CMTV_HD void h_sums_pipe(Walk& rd, int W, bool lead, const Store& store, const Barrier& barrier) {
+  fe e, f, g, h;
+  int dA, dR;
+  auto front = [&] {
+    rd.next(dA, dR);
+    h_window_addend_front(e, f, g, h, rd, dA, dR, rd.r_flip);
+    rd.next(dA, dR);  // the other wave's pair
+  };
+  if (lead)
+    front();
+  else
+    rd.next(dA, dR);
+#pragma unroll 1
+  for (int win = W - 2; win >= 0; win--) {
+    if (h_sums_pipe_owns(W, win, lead)) {
+      fe out[4];
+      h_window_addend_back(out, e, f, g, h);
+      store(win, out);
+    } else if (win > 0) {
+      front();
+    }
+    barrier(win);
+  }
+}
+
 // The quad side of the helper-summed verifiers after the decode (v: this
 // lane's coordinate of -A, rc: of -R, both extended, Z = 1): both tables,
 // then get_prep (the scalars; flags bits 16..23 carry the window count W the

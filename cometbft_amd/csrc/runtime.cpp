@@ -270,6 +270,7 @@ static void read_env(cmtv_ctx* ctx) {
   env_not("CMTV_HS_SUM_SPLIT", '0', ctx->hs_sum_split);
   env_is("CMTV_FORCE_FG_LATE", '1', ctx->fg_late);
   if (ctx->fg_late && !std::getenv("CMTV_HS_SUM_SPLIT")) ctx->hs_sum_split = true;
+  env_not("CMTV_HS_SUM_PIPE", '0', ctx->hs_sum_pipe);
   {
     uint32_t ft = 0;
     env_int("CMTV_HS_FOLD_TUNE", 0, 7, ft);

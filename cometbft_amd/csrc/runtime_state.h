@@ -443,6 +443,10 @@ struct cmtv_ctx {
   // falls back on every window (it turns the split on unless the other knob
   // says 0)
   bool hs_sum_split = false, fg_late = false;
+  // CMTV_HS_SUM_PIPE: the two waves form every second window's sum each, half
+  // a sum per window (hs_helper.h hs_helper_sums_pipe); 0 = the hash helper
+  // forms them alone. The split above, where it is on, takes precedence
+  bool hs_sum_pipe = true;
   // diag[kDiagLateSum] of every device, summed by read_diag (cmtv_late_sum_waves)
   uint64_t late_sum_waves = 0;
   size_t lane_chunk = cmtv::kChunk;         // signatures per lane-kernel launch (env CMTV_LANE_CHUNK)

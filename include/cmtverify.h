@@ -168,7 +168,10 @@ typedef struct cmtv_device_stats {
  * window sum with the comb wave instead of forming it alone; off by default),
  * CMTV_FORCE_FG_LATE=1 (test knob: that split with the comb wave's half
  * never arriving, so the hash helper forms every sum alone on its fallback
- * path, counted by cmtv_late_sum_waves), CMTV_HS_FOLD=0 (the Ed25519 quad kernel keeps [u]B as a term of
+ * path, counted by cmtv_late_sum_waves), CMTV_HS_SUM_PIPE=0 (that kernel's
+ * hash helper forms every window sum alone; by default it and the comb wave
+ * form every second one each, half a sum per window; without effect under
+ * CMTV_HS_SUM_SPLIT=1), CMTV_HS_FOLD=0 (the Ed25519 quad kernel keeps [u]B as a term of
  * its windows: k_verify_quad_hs instead of k_verify_quad_hs_fold),
  * CMTV_RCCL_LIB=path (the RCCL library to dlopen
  * instead of the system librccl; with CMTV_FORCE_RCCL a repeated ordinal then

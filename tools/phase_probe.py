@@ -22,7 +22,8 @@ which of them waits, and for how long.
 [s]B published; the hash helper 3 = its last sum, 7 = cycles at the window
 barriers, 4 = cycles at its polls for the comb wave's F and G (the split
 window sums); the quads 3 = cycles at the flag, 4 = P_s taken, 5 = exit, 7 as
-the helper. Printed: barrier 1 per role, the comb wave's finish, the quads'
+the helper; the comb wave 7 as the helper when it forms every second window
+sum (the pipelined sums, CMTV_HS_SUM_PIPE). Printed: barrier 1 per role, the comb wave's finish, the quads'
 wait at the flag, the loop length, the waits at the window barriers and at the
 F/G poll, and which wave shares the comb wave's SIMD.
 """
@@ -63,6 +64,8 @@ def fold_report(st, helper_wave):
         "helper_window_wait_median": float(np.median(win_wait[:, helper_wave])),
         "helper_fg_wait_median": float(np.median(fg_wait)), "helper_fg_wait_max": int(fg_wait.max()),
         "quad_window_wait_median": float(np.median(win_wait[:, quads])),
+        # the comb wave's, when it takes part in the window sums (CMTV_HS_SUM_PIPE; else slot 7 is never written)
+        "comb_window_wait_median": float(np.median(win_wait[:, 4])),
         "waves_sharing_comb_simd": {"wave%d" % w: shares[w] for w in range(4)}, "workgroups": int(st.shape[0]),
         "median_wg": {"index": med, "helper_at_b1": int(h[med, 1]), "quads_at_b1": [int(x) for x in q[med, :, 1]],
                       "comb_published": int(c[med, 3]), "b1_release": int(rel[med]),
