@@ -365,6 +365,42 @@ class Context:
         N.check(rc, "cmtv_sign_ed25519")
         return out[:n]
 
+    def pubkeys_secp256k1(self, priv: np.ndarray, with_addresses: bool = False):
+        """The 33-byte compressed keys of n 32-byte big-endian private keys in
+        [1, n - 1] (PrivKey.PubKey, crypto/secp256k1/secp256k1.go:45), made on
+        the device; with_addresses also their 20-byte addresses
+        (PubKey.Address, secp256k1.go:156). Test data only: variable time."""
+        priv = np.ascontiguousarray(priv, dtype=np.uint8).reshape(-1, 32)
+        n = priv.shape[0]
+        pk = np.zeros((max(n, 1), SECP256K1_PUBKEY_SIZE), np.uint8)
+        addr = np.zeros((max(n, 1), 20), np.uint8) if with_addresses else None
+        rc = N.lib().cmtv_pubkeys_secp256k1(self._h, n, _u8(priv), _u8(pk), _u8(addr) if with_addresses else None)
+        N.check(rc, "cmtv_pubkeys_secp256k1")
+        return (pk[:n], addr[:n]) if with_addresses else pk[:n]
+
+    def sign_secp256k1(self, priv: np.ndarray, msg: np.ndarray, msg_off: np.ndarray, key_idx=None) -> np.ndarray:
+        """r || s signatures (PrivKey.Sign, secp256k1.go:128: RFC 6979 nonces,
+        lower-S) made on the device; signature i by priv[key_idx[i]] (None:
+        by priv[i]) over msg[msg_off[i]:msg_off[i + 1]]. Test data only."""
+        priv = np.ascontiguousarray(priv, dtype=np.uint8).reshape(-1, 32)
+        off = np.ascontiguousarray(msg_off, dtype=np.uint32)
+        n = len(off) - 1
+        msg = np.ascontiguousarray(msg, dtype=np.uint8)
+        if msg.size == 0:
+            msg = np.zeros(1, np.uint8)
+        out = np.zeros((max(n, 1), 64), np.uint8)
+        u32p = ctypes.POINTER(ctypes.c_uint32)
+        kp = None
+        if key_idx is not None:
+            key_idx = np.ascontiguousarray(key_idx, dtype=np.uint32)
+            if key_idx.shape[0] != n:
+                raise ValueError("key_idx / msg_off sizes disagree")
+            kp = key_idx.ctypes.data_as(u32p)
+        rc = N.lib().cmtv_sign_secp256k1(self._h, priv.shape[0], _u8(priv), n, kp, _u8(msg), off.ctypes.data_as(u32p),
+                                         _u8(out))
+        N.check(rc, "cmtv_sign_secp256k1")
+        return out[:n]
+
 
 class KeySet:
     """Registered public keys (cmtv_keyset): per-key combs resident in HBM."""
@@ -465,6 +501,16 @@ def default_context() -> Context:
         if _default_ctx is None:
             _default_ctx = Context()
         return _default_ctx
+
+
+def secp256k1_privkey_from_secret(secret: bytes) -> bytes:
+    """GenPrivKeySecp256k1 (crypto/secp256k1/secp256k1.go:107):
+    (SHA-256(secret) mod (n - 1)) + 1 as 32 big-endian bytes."""
+    secret = bytes(secret)
+    buf = (ctypes.c_uint8 * max(len(secret), 1)).from_buffer_copy(secret or b"\0")
+    out = (ctypes.c_uint8 * 32)()
+    N.check(N.lib().cmtv_privkey_secp256k1_from_secret(buf, len(secret), out), "cmtv_privkey_secp256k1_from_secret")
+    return bytes(out)
 
 
 def pack_messages(msgs: Sequence[bytes]):

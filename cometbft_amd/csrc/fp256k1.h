@@ -13,6 +13,7 @@
 //   fp_neg(m)   : 2 (m + 1) p - a for a of magnitude <= m; output m + 1
 //   fp_sub(m)   : a + fp_neg(b, m)
 //   fp_normalize: any magnitude <= 16 -> the canonical value in [0, p)
+//   fp_invert   : input of magnitude <= 8; output 1
 // The point formulas in secp256k1.h state the magnitude of every operand;
 // CMTV_BOUNDS_CHECK builds (tests/host/secpcheck.cpp) assert them.
 //
@@ -263,6 +264,46 @@ CMTV_HD void fp_sqrt_candidate(fp& r, const fp& a) {
   fp_sqn(t, t, 6);
   fp_mul(t, t, x2);
   fp_sqn(r, t, 2);
+}
+
+// r = a^(p - 2) = 1 / a (0 for a = 0). a of magnitude <= 8 (fp_mul's bound);
+// output magnitude 1. Fixed chain over the exponent's runs of ones (223 and 22
+// ones, then the low ten bits 0000101101): 255 squarings, 15 multiplications.
+// The chain up to x223 is fp_sqrt_candidate's (kept apart so the verifier's
+// code stays as it was).
+CMTV_HD void fp_invert(fp& r, const fp& a) {
+  CMTV_ASSERT(fp_within(a, FP_MAX_MAG));
+  fp x2, x3, x22, x44, x88, t;
+  fp_sq(t, a);
+  fp_mul(x2, t, a);
+  fp_sq(t, x2);
+  fp_mul(x3, t, a);
+  fp_sqn(t, x3, 3);
+  fp_mul(t, t, x3);  // x6
+  fp_sqn(t, t, 3);
+  fp_mul(t, t, x3);  // x9
+  fp_sqn(t, t, 2);
+  fp_mul(t, t, x2);  // x11
+  fp_sqn(x22, t, 11);
+  fp_mul(x22, x22, t);
+  fp_sqn(x44, x22, 22);
+  fp_mul(x44, x44, x22);
+  fp_sqn(x88, x44, 44);
+  fp_mul(x88, x88, x44);
+  fp_sqn(t, x88, 88);
+  fp_mul(t, t, x88);  // x176
+  fp_sqn(t, t, 44);
+  fp_mul(t, t, x44);  // x220
+  fp_sqn(t, t, 3);
+  fp_mul(t, t, x3);  // x223
+  fp_sqn(t, t, 23);
+  fp_mul(t, t, x22);
+  fp_sqn(t, t, 5);
+  fp_mul(t, t, a);
+  fp_sqn(t, t, 3);
+  fp_mul(t, t, x2);
+  fp_sqn(t, t, 2);
+  fp_mul(r, t, a);
 }
 
 }  // namespace cmtv

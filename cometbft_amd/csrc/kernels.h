@@ -194,6 +194,14 @@ hipError_t launch_bulk_gather(uint32_t n_c, uint32_t m, const void* desc, const 
 hipError_t launch_pubkey(uint32_t n, const void* seeds, const uint32_t* btab, void* out_pk, hipStream_t s);
 hipError_t launch_sign(uint32_t n, const void* seeds, const void* key_idx, const void* msg, const void* off,
                        const uint32_t* btab, void* out_sig, hipStream_t s);
+// secp256k1 test data (secp256k1_sign.hip): priv n x 32 bytes big-endian, every
+// key in [1, n - 1] (the caller checked); gtab the verifier's fixed table.
+// out_pk n x 33 bytes, out_addr n x 20 bytes (4-byte aligned) or null.
+hipError_t launch_secp_pubkey(uint32_t n, const void* priv, const uint32_t* gtab, void* out_pk, void* out_addr,
+                              hipStream_t s);
+// signature i by key key_idx[i] (null: key i) over msg[off[i] .. off[i + 1]); out_sig n x 64 bytes (4-byte aligned)
+hipError_t launch_secp_sign(uint32_t n, const void* priv, const void* key_idx, const void* msg, const void* off,
+                            const uint32_t* gtab, void* out_sig, hipStream_t s);
 
 // One pass of the merkle engine (merkle.hip, merkle.h): n_wg workgroups, each
 // an aligned block of one tree's leaves reduced to node g of `out` (8 words a

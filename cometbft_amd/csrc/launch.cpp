@@ -42,6 +42,13 @@ struct LaunchScope {
     D.signatures += n;
     return CMTV_OK;
   }
+  // the end of a call that verifies nothing (test-data generation): timed
+  // like the others, not counted among the verification calls
+  int finish_uncounted() {
+    hipError_t e;
+    if (timed && (e = D.timing.end(tp, s)) != hipSuccess) return hip_fail(e);
+    return CMTV_OK;
+  }
 };
 
 // An armed host batch's tagged bitmap (CmtvDev::tag_arm) taken by a launch:
@@ -358,6 +365,71 @@ int enqueue_verify_secp_templated(cmtv_ctx* ctx, CmtvDev& D, size_t n, const uin
     return enqueue_verify_secp_keyed(ctx, D, ks, n, d_idx, d_sig, d_msg, d_off, d_valid, d_bitmap, s,
                                      fuse ? &sb : nullptr, batch);
   return enqueue_verify_secp(ctx, D, n, d_pk, d_sig, d_msg, d_off, d_valid, d_bitmap, s, fuse ? &sb : nullptr);
+}
+
+// ---------------------------------------------------------------- secp256k1 test data
+// cmtv_pubkeys_secp256k1 / cmtv_sign_secp256k1 behind their argument checks
+// (runtime.cpp), after the Ed25519 pair there: host buffers in and out, one
+// launch per kChunk on D's stream, waited for. The comb runs over the
+// verifier's fixed table.
+
+int secp_pubkeys_host_locked(cmtv_ctx* ctx, CmtvDev& D, size_t n, const uint8_t* priv, uint8_t* out_pk,
+                             uint8_t* out_addr) {
+  hipError_t e = ensure_secp_gtab(D);
+  if (e != hipSuccess) return hip_fail(e);
+  const size_t o_addr = align_up(33 * n, 256);
+  if ((e = D.d_in.ensure(32 * n)) != hipSuccess) return hip_fail(e);
+  if ((e = D.d_out.ensure(o_addr + (out_addr ? 20 * n : 0))) != hipSuccess) return hip_fail(e);
+  auto* dout = static_cast<uint8_t*>(D.d_out.p);
+  if ((e = hipMemcpyAsync(D.d_in.p, priv, 32 * n, hipMemcpyHostToDevice, D.stream)) != hipSuccess)
+    return hip_fail(e);
+  LaunchScope L{ctx, D, D.stream};
+  if ((e = L.begin()) != hipSuccess) return hip_fail(e);
+  for (size_t c = 0; c < n; c += kChunk) {
+    const uint32_t cn = (uint32_t)std::min<size_t>(kChunk, n - c);
+    e = launch_secp_pubkey(cn, static_cast<uint8_t*>(D.d_in.p) + 32 * c, D.d_secp_gtab, dout + 33 * c,
+                           out_addr ? dout + o_addr + 20 * c : nullptr, D.stream);
+    if ((e = L.launched(e)) != hipSuccess) return hip_fail(e);
+  }
+  if (const int rc = L.finish_uncounted()) return rc;
+  if ((e = hipMemcpyAsync(out_pk, dout, 33 * n, hipMemcpyDeviceToHost, D.stream)) != hipSuccess) return hip_fail(e);
+  if (out_addr &&
+      (e = hipMemcpyAsync(out_addr, dout + o_addr, 20 * n, hipMemcpyDeviceToHost, D.stream)) != hipSuccess)
+    return hip_fail(e);
+  if ((e = hipStreamSynchronize(D.stream)) != hipSuccess) return hip_fail(e);
+  return CMTV_OK;
+}
+
+int secp_sign_host_locked(cmtv_ctx* ctx, CmtvDev& D, size_t n_keys, const uint8_t* priv, size_t n,
+                          const uint32_t* key_idx, const uint8_t* msg, const uint32_t* msg_off, uint8_t* out_sig) {
+  hipError_t e = ensure_secp_gtab(D);
+  if (e != hipSuccess) return hip_fail(e);
+  const size_t msg_bytes = msg_off[n];
+  const size_t o_idx = align_up(32 * n_keys, 256), o_off = align_up(o_idx + (key_idx ? 4 * n : 0), 256);
+  const size_t o_msg = align_up(o_off + 4 * (n + 1), 256), in_bytes = align_up(o_msg + msg_bytes + 16, 256);
+  if ((e = D.h_in.ensure(in_bytes)) != hipSuccess) return hip_fail(e);
+  if ((e = D.d_in.ensure(in_bytes)) != hipSuccess) return hip_fail(e);
+  if ((e = D.d_out.ensure(64 * n)) != hipSuccess) return hip_fail(e);
+  auto* hin = static_cast<uint8_t*>(D.h_in.p);
+  std::memcpy(hin, priv, 32 * n_keys);
+  if (key_idx) std::memcpy(hin + o_idx, key_idx, 4 * n);
+  std::memcpy(hin + o_off, msg_off, 4 * (n + 1));
+  if (msg_bytes) std::memcpy(hin + o_msg, msg, msg_bytes);
+  auto* din = static_cast<uint8_t*>(D.d_in.p);
+  if ((e = hipMemcpyAsync(din, hin, in_bytes, hipMemcpyHostToDevice, D.stream)) != hipSuccess) return hip_fail(e);
+  LaunchScope L{ctx, D, D.stream};
+  if ((e = L.begin()) != hipSuccess) return hip_fail(e);
+  for (size_t c = 0; c < n; c += kChunk) {
+    const uint32_t cn = (uint32_t)std::min<size_t>(kChunk, n - c);
+    e = launch_secp_sign(cn, key_idx ? din : din + 32 * c, key_idx ? din + o_idx + 4 * c : nullptr, din + o_msg,
+                         din + o_off + 4 * c, D.d_secp_gtab, static_cast<uint8_t*>(D.d_out.p) + 64 * c, D.stream);
+    if ((e = L.launched(e)) != hipSuccess) return hip_fail(e);
+  }
+  if (const int rc = L.finish_uncounted()) return rc;
+  if ((e = hipMemcpyAsync(out_sig, D.d_out.p, 64 * n, hipMemcpyDeviceToHost, D.stream)) != hipSuccess)
+    return hip_fail(e);
+  if ((e = hipStreamSynchronize(D.stream)) != hipSuccess) return hip_fail(e);
+  return CMTV_OK;
 }
 
 }  // namespace cmtv

@@ -23,6 +23,7 @@
 #include "runtime_state.h"
 // (after the HIP runtime's header)
 #include "merlin.h"
+#include "secp256k1_sign.h"
 
 namespace cmtv {
 
@@ -819,6 +820,53 @@ int cmtv_sign_ed25519(cmtv_ctx* ctx, size_t n, const uint8_t* seeds, const uint3
     return hip_fail(e);
   if ((e = hipStreamSynchronize(D.stream)) != hipSuccess) return hip_fail(e);
   return CMTV_OK;
+}
+
+int cmtv_privkey_secp256k1_from_secret(const uint8_t* secret, size_t len, uint8_t out_priv[32]) {
+  if (!out_priv || (len && !secret) || len > (1ull << 31)) return CMTV_EINVAL;
+  // sha256_msg reads whole aligned words around its message: a copy of our own
+  std::vector<uint32_t> buf(len / 4 + 2, 0u);
+  if (len) std::memcpy(buf.data(), secret, len);
+  uint32_t c[8];
+  sha256_msg(c, reinterpret_cast<const uint8_t*>(buf.data()), (uint32_t)len);
+  secp_privkey_from_digest(out_priv, c);
+  return CMTV_OK;
+}
+
+// the device both secp256k1 test-data calls run on: the first live one, made current
+static int secp_testdata_dev(cmtv_ctx* ctx, std::unique_lock<std::mutex>& lk, CmtvDev*& D) {
+  if (ctx_lock(ctx, lk) != CMTV_OK) return CMTV_ENODEV;
+  if (ctx->live.empty()) return CMTV_ENODEV;
+  D = &ctx->devs[ctx->live[0]];
+  return hipSetDevice(D->ordinal) == hipSuccess ? CMTV_OK : CMTV_ENODEV;
+}
+
+int cmtv_pubkeys_secp256k1(cmtv_ctx* ctx, size_t n, const uint8_t* priv, uint8_t* out_pk, uint8_t* out_addr) {
+  if (!ctx || n > (1ull << 31)) return CMTV_EINVAL;
+  if (n == 0) return CMTV_OK;
+  if (!priv || !out_pk) return CMTV_EINVAL;
+  for (size_t i = 0; i < n; i++)
+    if (!secp_privkey_in_range(priv + 32 * i)) return CMTV_EINVAL;
+  std::unique_lock<std::mutex> lk;
+  CmtvDev* D = nullptr;
+  if (const int rc = secp_testdata_dev(ctx, lk, D)) return rc;
+  return secp_pubkeys_host_locked(ctx, *D, n, priv, out_pk, out_addr);
+}
+
+int cmtv_sign_secp256k1(cmtv_ctx* ctx, size_t n_keys, const uint8_t* priv, size_t n, const uint32_t* key_idx,
+                        const uint8_t* msg, const uint32_t* msg_off, uint8_t* out_sig) {
+  if (!ctx || n > (1ull << 31) || n_keys > (1ull << 31)) return CMTV_EINVAL;
+  if (!key_idx && n != n_keys) return CMTV_EINVAL;
+  if (n == 0) return CMTV_OK;
+  if (!priv || !msg_off || !out_sig || n_keys == 0 || (!msg && msg_off[n] != 0)) return CMTV_EINVAL;
+  for (size_t i = 0; i < n; i++)
+    if (msg_off[i + 1] < msg_off[i] || (key_idx && key_idx[i] >= n_keys)) return CMTV_EINVAL;
+  for (size_t i = 0; i < n_keys; i++)
+    if (!secp_privkey_in_range(priv + 32 * i)) return CMTV_EINVAL;
+  std::unique_lock<std::mutex> lk;
+  CmtvDev* D = nullptr;
+  if (const int rc = secp_testdata_dev(ctx, lk, D)) return rc;
+  return secp_sign_host_locked(ctx, *D, n_keys, priv, n, key_idx, msg, msg_off, out_sig);
 }
 
 }  // extern "C"

@@ -745,6 +745,13 @@ int enqueue_verify_secp_templated(cmtv_ctx* ctx, CmtvDev& D, size_t n, const uin
                                   const cmtv_secp_keyset* ks, const uint32_t* d_idx, const uint8_t* d_sig,
                                   const SbFuse& sb, uint32_t max_len, const uint32_t* d_off, uint8_t* d_msg,
                                   uint8_t* d_valid, uint64_t* d_bitmap, hipStream_t s, bool batch = false);
+// secp256k1 test data (secp256k1_sign.hip) from host buffers, on device D
+// (current on this thread), blocking, in launches of kChunk; the arguments
+// checked by the caller (runtime.cpp). Lock held.
+int secp_pubkeys_host_locked(cmtv_ctx* ctx, CmtvDev& D, size_t n, const uint8_t* priv, uint8_t* out_pk,
+                             uint8_t* out_addr);
+int secp_sign_host_locked(cmtv_ctx* ctx, CmtvDev& D, size_t n_keys, const uint8_t* priv, size_t n,
+                          const uint32_t* key_idx, const uint8_t* msg, const uint32_t* msg_off, uint8_t* out_sig);
 
 // host_batch.cpp: a host batch straight to the devices (no verdict cache),
 // generic keys or (ks) registered ones; secp256k1 on devs[0]. Lock held.

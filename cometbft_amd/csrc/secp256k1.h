@@ -352,6 +352,32 @@ CMTV_HD bool secp_verify_one(const uint8_t* pk, const uint8_t* sig, const uint8_
   return secp_x_is_r(acc, r) && ok;
 }
 
+#ifdef __HIPCC__
+// The GTab policy of the kernels (secp256k1.hip, secp256k1_sign.hip): the
+// fixed table's, or a registered key's, 32-word rows gathered with dwordx4 loads
+struct DevSecpGTab {
+  const uint32_t* __restrict__ rows;
+  __device__ __forceinline__ void load(int row, pt256& p) const {
+    const uint4* q = reinterpret_cast<const uint4*>(rows + (size_t)row * SECP_GTAB_ROW_WORDS);
+    uint32_t w[32];
+#pragma unroll
+    for (int k = 0; k < 8; k++) {
+      const uint4 v = q[k];
+      w[4 * k] = v.x;
+      w[4 * k + 1] = v.y;
+      w[4 * k + 2] = v.z;
+      w[4 * k + 3] = v.w;
+    }
+#pragma unroll
+    for (int i = 0; i < 10; i++) {
+      p.X.v[i] = w[i];
+      p.Y.v[i] = w[10 + i];
+      p.Z.v[i] = w[20 + i];
+    }
+  }
+};
+#endif
+
 // ---------------------------------------------------------------- registered keys
 // A registered key Q has a comb table of its own in the fixed table's layout:
 // row (j, d) = [d 256^j]Q, j = 0..32, d = 1..128 (528 KiB per key). [u2]Q is

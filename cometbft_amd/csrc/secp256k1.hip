@@ -66,28 +66,6 @@ struct DevSecpQTab {
   }
 };
 
-struct DevSecpGTab {
-  const uint32_t* __restrict__ rows;
-  __device__ __forceinline__ void load(int row, pt256& p) const {
-    const uint4* q = reinterpret_cast<const uint4*>(rows + (size_t)row * SECP_GTAB_ROW_WORDS);
-    uint32_t w[32];
-#pragma unroll
-    for (int k = 0; k < 8; k++) {
-      const uint4 v = q[k];
-      w[4 * k] = v.x;
-      w[4 * k + 1] = v.y;
-      w[4 * k + 2] = v.z;
-      w[4 * k + 3] = v.w;
-    }
-#pragma unroll
-    for (int i = 0; i < 10; i++) {
-      p.X.v[i] = w[i];
-      p.Y.v[i] = w[10 + i];
-      p.Z.v[i] = w[20 + i];
-    }
-  }
-};
-
 __global__ __launch_bounds__(64) void k_secp_gtab_build(uint32_t* __restrict__ rows) {
   const uint32_t gid = blockIdx.x * 64 + threadIdx.x;
   if (gid >= (uint32_t)SECP_GTAB_ENTRIES) return;

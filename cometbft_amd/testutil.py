@@ -7,6 +7,11 @@ Keys and signatures are produced by the device (cmtv_pubkeys_ed25519 /
 cmtv_sign_ed25519 = RFC 8032 deterministic signing, identical to Go's Sign);
 sign-bytes by the library's CanonicalVote encoder.
 
+secp256k1 and mixed sets (make_secp256k1_validator_set / make_secp256k1_commit)
+are made the same way: private keys GenPrivKeySecp256k1("cmtverify/val/secp256k1/" || i)
+(crypto/secp256k1/secp256k1.go:107), keys, addresses and RFC 6979 signatures
+from the device (cmtv_pubkeys_secp256k1 / cmtv_sign_secp256k1).
+
 Workload definition:
   seed_i  = SHA-256("cmtverify/val/" || i), voting power 10, set sorted by address
   commit  = chain "cmtverify-bench", Precommit, round 0,
@@ -20,7 +25,7 @@ from dataclasses import dataclass
 
 import numpy as np
 
-from .crypto import Context, pack_messages
+from .crypto import Context, pack_messages, secp256k1_privkey_from_secret
 from .types import (BLOCK_ID_FLAG_COMMIT, PRECOMMIT_TYPE, BlockID, Commit, CommitSig, PartSetHeader, Validator,
                     ValidatorSet, vote_sign_bytes)
 
@@ -79,6 +84,58 @@ def make_commit(ctx: Context, sv: SyntheticValidators, height: int, round_: int 
     msgs = commit_messages(n, height, round_, chain_id, flags)
     m, off = pack_messages(msgs)
     sigs = ctx.sign(sv.seeds, m, off)
+    bid = block_id_for_height(height)
+    css = []
+    for i in range(n):
+        if flags[i] == 1:  # absent
+            css.append(CommitSig(1))
+        else:
+            css.append(CommitSig(flags[i], sv.valset.validators[i].address, timestamp(height, i), bytes(sigs[i])))
+    return Commit(height, round_, bid, css), msgs, sigs
+
+
+def secp256k1_validator_privkeys(n: int, offset: int = 0) -> np.ndarray:
+    return np.array([np.frombuffer(secp256k1_privkey_from_secret(b"cmtverify/val/secp256k1/%d" % (offset + i)), np.uint8)
+                     for i in range(n)], dtype=np.uint8).reshape(n, 32)
+
+
+@dataclass
+class SyntheticTypedValidators:
+    secrets: np.ndarray   # n x 32, in validator-set order: a secp256k1 private key or an Ed25519 seed
+    key_types: list       # n of "secp256k1" / "ed25519"
+    valset: ValidatorSet
+
+
+def make_secp256k1_validator_set(ctx: Context, n: int, power: int = 10, offset: int = 0,
+                                 n_ed25519: int = 0) -> SyntheticTypedValidators:
+    """n secp256k1 validators and, for a mixed set, n_ed25519 Ed25519 ones
+    (make_validator_set's seeds), sorted by address like NewValidatorSet."""
+    priv = secp256k1_validator_privkeys(n, offset)
+    pks, addrs = ctx.pubkeys_secp256k1(priv, with_addresses=True)
+    rows = [(bytes(a), bytes(pk), "secp256k1", priv[i]) for i, (pk, a) in enumerate(zip(pks, addrs))]
+    if n_ed25519:
+        seeds = validator_seeds(n_ed25519, offset)
+        for pk, seed in zip(ctx.pubkeys(seeds), seeds):
+            rows.append((hashlib.sha256(bytes(pk)).digest()[:20], bytes(pk), "ed25519", seed))
+    rows.sort(key=lambda r: r[0])
+    vals = ValidatorSet([Validator(pk, power, key_type=kt) for _, pk, kt, _ in rows])
+    secrets = np.array([r[3] for r in rows], np.uint8).reshape(len(rows), 32)
+    return SyntheticTypedValidators(secrets, [r[2] for r in rows], vals)
+
+
+def make_secp256k1_commit(ctx: Context, sv: SyntheticTypedValidators, height: int, round_: int = 0,
+                          chain_id: str = CHAIN_ID, flags=None):
+    """make_commit for a set of make_secp256k1_validator_set: (Commit, msgs,
+    sig array), every present validator signing with its own key type."""
+    n = len(sv.valset.validators)
+    flags = [BLOCK_ID_FLAG_COMMIT] * n if flags is None else list(flags)
+    msgs = commit_messages(n, height, round_, chain_id, flags)
+    sigs = np.zeros((n, 64), np.uint8)
+    for kt, sign in (("secp256k1", ctx.sign_secp256k1), ("ed25519", ctx.sign)):
+        idx = np.array([i for i in range(n) if sv.key_types[i] == kt], np.uint32)
+        if idx.size:
+            m, off = pack_messages([msgs[i] for i in idx])
+            sigs[idx] = sign(sv.secrets[idx], m, off)
     bid = block_id_for_height(height)
     css = []
     for i in range(n):

@@ -790,6 +790,38 @@ int cmtv_pubkeys_ed25519(cmtv_ctx* ctx, size_t n, const uint8_t* seeds, uint8_t*
 int cmtv_sign_ed25519(cmtv_ctx* ctx, size_t n, const uint8_t* seeds, const uint32_t* key_idx, const uint8_t* msg,
                       const uint32_t* msg_off, uint8_t* out_sig);
 
+/* The same for secp256k1 (the reference's GenPrivKeySecp256k1, PrivKey.PubKey,
+ * PubKey.Address and PrivKey.Sign, crypto/secp256k1/secp256k1.go:107,45,156,128).
+ *
+ * NOT A SIGNER FOR KEYS THAT MATTER. The kernels are variable-time (table
+ * lookups by secret digits, branches on secret data), and the private keys
+ * are copied into the HBM of a device other processes may share. These calls
+ * make synthetic validator sets and commits for tests and benchmarks.
+ *
+ * A private key is 32 bytes big-endian, a value in [1, n - 1] (n the group
+ * order). cmtv_privkey_secp256k1_from_secret is GenPrivKeySecp256k1:
+ * (SHA-256(secret) mod (n - 1)) + 1; host only, no context.
+ * cmtv_pubkeys_secp256k1: the 33-byte compressed keys (0x02 | (y & 1), x) and,
+ * when out_addr is not NULL, the addresses RIPEMD-160(SHA-256(key)).
+ * cmtv_sign_secp256k1: r || s, 32 bytes big-endian each, over SHA-256(msg),
+ * with the deterministic nonce of RFC 6979 section 3.2 (HMAC-SHA-256, no
+ * extra data) and s in the lower half. Signature i is by priv[key_idx[i]] over
+ * msg[msg_off[i] .. msg_off[i + 1]); key_idx NULL: n == n_keys and signature i
+ * is by key i. (btcec's bytes, which the reference signs with, are not in the
+ * tree to compare against: DESIGN 2.)
+ *
+ * Both device calls are blocking, take and fill host buffers and run on the
+ * context's first live device. CMTV_EINVAL, checked before any device work
+ * and with nothing written: a NULL required pointer, n > 2^31, a decreasing
+ * msg_off, a key_idx[i] >= n_keys, key_idx NULL with n != n_keys, a private
+ * key that is 0 or >= n. n == 0 is CMTV_OK. */
+int cmtv_privkey_secp256k1_from_secret(const uint8_t* secret, size_t len, uint8_t out_priv[32]);
+int cmtv_pubkeys_secp256k1(cmtv_ctx* ctx, size_t n, const uint8_t* priv /* n x 32 */, uint8_t* out_pk /* n x 33 */,
+                           uint8_t* out_addr /* n x 20, or NULL */);
+int cmtv_sign_secp256k1(cmtv_ctx* ctx, size_t n_keys, const uint8_t* priv /* n_keys x 32 */, size_t n,
+                        const uint32_t* key_idx /* n, or NULL */, const uint8_t* msg,
+                        const uint32_t* msg_off /* n + 1 */, uint8_t* out_sig /* n x 64 */);
+
 #ifdef __cplusplus
 }
 #endif

@@ -5,7 +5,7 @@ existed: cmtv_vote_sign_bytes per signature, the messages packed, and
 cmtv_verify_secp256k1 (key bytes) or cmtv_verify_secp256k1_indexed
 (registered keys) over them. Needs a GPU; there is no CPU fallback.
 
-    python tools/bench_typed_commit.py [--sizes 150,10000] [--reps 200,40] [--warmup 10]
+    python tools/bench_typed_commit.py [--sizes 150,10000] [--reps 200,40] [--warmup 10] [--real-keys]
 
 Per size, four timed calls alternate in one loop, each a host clock around
 a call that returns after its verdicts are back:
@@ -26,6 +26,10 @@ index of a bad one, the composed calls all-valid and exactly that index
 invalid, and a sample of signatures is verified with tests/secp256k1_ref.py.
 The keys are consecutive multiples of G and every signature uses one nonce
 (valid ECDSA, cheap to make: the verifier's work does not depend on either).
+--real-keys takes the set and the signatures from the device signer instead
+(testutil.make_secp256k1_validator_set: derived keys in address order, RFC 6979
+nonces); the default stays the cheap construction so recorded numbers remain
+comparable.
 """
 from __future__ import annotations
 
@@ -82,6 +86,7 @@ def main():
     ap.add_argument("--sizes", default="150,10000")
     ap.add_argument("--reps", default="200,40")
     ap.add_argument("--warmup", type=int, default=10)
+    ap.add_argument("--real-keys", action="store_true", help="derived keys and RFC 6979 nonces from the device signer")
     args = ap.parse_args()
     sizes = [int(x) for x in args.sizes.split(",")]
     reps = [int(x) for x in args.reps.split(",")]
@@ -102,8 +107,13 @@ def main():
     ctx_off, ctx_on = Context(device=0), Context(device=0)
     ctx_on.keyset_cache(2)
     for n, rep in zip(sizes, reps):
-        privs, pks = make_set(n)
-        vals = T.ValidatorSet([T.Validator(pk, 10, 0, "secp256k1") for pk in pks])
+        if args.real_keys:
+            sv = TU.make_secp256k1_validator_set(ctx_off, n)
+            vals = sv.valset
+            pks = [v.pub_key for v in vals.validators]
+        else:
+            privs, pks = make_set(n)
+            vals = T.ValidatorSet([T.Validator(pk, 10, 0, "secp256k1") for pk in pks])
         bid = TU.block_id_for_height(HEIGHT)
         stamps = [TU.timestamp(HEIGHT, i) for i in range(n)]
 
@@ -119,7 +129,8 @@ def main():
             return pack_messages(out), out
 
         (m, off), msgs = encode_all()
-        sigs = sign_all(privs, msgs)
+        sigs = [bytes(x) for x in ctx_off.sign_secp256k1(sv.secrets, m, off)] if args.real_keys else \
+            sign_all(privs, msgs)
         for i in range(0, n, max(1, n // 50)):  # a sample against the reference verifier
             assert S.verify(pks[i], msgs[i], sigs[i]), i
         bad_at = n - 3 if n > 3 else 0
@@ -192,7 +203,7 @@ def main():
         med = {k: float(np.median(v)) * 1e3 for k, v in times.items()}
         sb_ms = float(np.median(sb)) * 1e3
         print(json.dumps({
-            "tool": "bench_typed_commit", "n": n, "reps": rep, "msg_len": len(msgs[0]),
+            "tool": "bench_typed_commit", "real_keys": args.real_keys, "n": n, "reps": rep, "msg_len": len(msgs[0]),
             **{k + "_ms": round(v, 4) for k, v in med.items()},
             **{k + "_p90_ms": round(float(np.percentile(times[k], 90)) * 1e3, 4) for k in times},
             "parent_signbytes_ms": round(sb_ms, 4),

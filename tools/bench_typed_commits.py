@@ -7,6 +7,7 @@ one inversion mod n) against the one-signature-per-lane kernel inside the
 same call. Needs a GPU; there is no CPU fallback.
 
     python tools/bench_typed_commits.py [--heights 67,700,1400,7000,14000] [--reps 30,10,8,5,4] [--warmup 2]
+                                        [--real-keys]
 
 Per number of heights H, the sides alternate in one loop, each a host clock
 around a call that returns after its verdicts are back; medians are reported:
@@ -29,7 +30,10 @@ CMTV_OK for every height of the good chain and "wrong signature (#i)" at the
 flipped index of three heights of a bad one. Keys are consecutive multiples of
 G, every signature uses one nonce and all validators of a height sign at one
 timestamp (valid ECDSA, cheap to make: the verifier's work depends on none of
-it).
+it). --real-keys builds the chain with the device signer instead
+(testutil.make_secp256k1_validator_set: distinct derived keys in address order,
+RFC 6979 nonces, a timestamp per validator), to measure that claim; the default
+stays the cheap construction so recorded numbers remain comparable.
 """
 from __future__ import annotations
 
@@ -87,7 +91,7 @@ class Chain:
     """H heights of one validator set as a cgo shim would hand them over:
     flat arrays, one cmtv_commit / cmtv_valset / cmtv_block_id per height."""
 
-    def __init__(self, n_heights):
+    def __init__(self, n_heights, real_ctx=None):
         import secp256k1_ref as S
         from bench_typed_commit import make_set
         from cometbft_amd import _native as N
@@ -95,6 +99,14 @@ class Chain:
         from cometbft_amd import types as T
 
         n, H = N_VALS, n_heights
+        self.N, self.H = N, H
+        self.flags = np.full(n + 1, T.BLOCK_ID_FLAG_COMMIT, np.uint8)
+        self.sig_off = (64 * np.arange(n + 1)).astype(np.uint32)
+        self.addrs = np.zeros(20 * n + 1, np.uint8)
+        self.bad = None
+        if real_ctx is not None:
+            self._init_real(real_ctx, S, TU)
+            return
         privs, pks = make_set(n)
         self.vals = T.ValidatorSet([T.Validator(pk, 10, 0, "secp256k1") for pk in pks])
         self.vs, self._keep_v = self.vals._pack()
@@ -105,9 +117,6 @@ class Chain:
         ki = pow(k, S.N - 2, S.N)
         rb = r.to_bytes(32, "big")
         rd = [r * d % S.N for d in privs]
-        self.flags = np.full(n + 1, T.BLOCK_ID_FLAG_COMMIT, np.uint8)
-        self.sig_off = (64 * np.arange(n + 1)).astype(np.uint32)
-        self.addrs = np.zeros(20 * n + 1, np.uint8)
         self.secs = np.zeros((H, n), np.int64)
         self.nanos = np.zeros((H, n), np.int32)
         self.hashes = np.zeros((H, 2, 32), np.uint8)
@@ -134,8 +143,37 @@ class Chain:
             assert S.verify(pk, msg, sig)
         self.msg_len = len(msg)
         self.good = np.frombuffer(bytes(sigs), np.uint8).reshape(H, 64 * n).copy()
-        self.bad = None
-        self.N, self.H = N, H
+
+    def _init_real(self, ctx, S, TU, sign_heights=2048):
+        """The same arrays from the device signer: derived keys, RFC 6979
+        nonces, validator i of height h signing at testutil.timestamp(h, i)."""
+        n, H = N_VALS, self.H
+        sv = TU.make_secp256k1_validator_set(ctx, n)
+        self.vals = sv.valset
+        self.vs, self._keep_v = self.vals._pack()
+        self.kt = self._keep_v[5].ctypes.data_as(ctypes.POINTER(ctypes.c_uint8))
+        self.addrs[:20 * n] = np.frombuffer(b"".join(v.address for v in self.vals.validators), np.uint8)
+        ts = [[TU.timestamp(H0 + h, i) for i in range(n)] for h in range(H)]
+        self.secs = np.array([[t[0] for t in row] for row in ts], np.int64)
+        self.nanos = np.array([[t[1] for t in row] for row in ts], np.int32)
+        self.hashes = np.zeros((H, 2, 32), np.uint8)
+        for h in range(H):
+            bid = TU.block_id_for_height(H0 + h)
+            self.hashes[h, 0] = np.frombuffer(bid.hash, np.uint8)
+            self.hashes[h, 1] = np.frombuffer(bid.part_set_header.hash, np.uint8)
+        self.good = np.zeros((H, 64 * n), np.uint8)
+        self.sample = []
+        for c0 in range(0, H, sign_heights):
+            hc = min(sign_heights, H - c0)
+            m, off = TU.replay_messages(H0 + c0, hc, n)
+            kidx = np.tile(np.arange(n, dtype=np.uint32), hc)
+            self.good[c0:c0 + hc] = ctx.sign_secp256k1(sv.secrets, m, off, kidx).reshape(hc, 64 * n)
+            i = c0 % n
+            self.sample.append((self.vals.validators[i].pub_key, m[off[i]:off[i + 1]].tobytes(),
+                                self.good[c0, 64 * i: 64 * i + 64].tobytes()))
+        self.msg_len = int(off[1] - off[0])
+        for pk, msg, sig in self.sample:  # a sample against the reference verifier
+            assert S.verify(pk, msg, sig)
 
     def args(self, n_heights, sigs):
         """The C arrays of the first n_heights heights over the signature block `sigs`."""
@@ -166,6 +204,8 @@ def main():
     ap.add_argument("--heights", default="67,700,1400,7000,14000")
     ap.add_argument("--reps", default="30,10,8,5,4")
     ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--real-keys", action="store_true",
+                    help="derived keys, RFC 6979 nonces and per-validator timestamps from the device signer")
     args = ap.parse_args()
     hs = [int(x) for x in args.heights.split(",")]
     reps = [int(x) for x in args.reps.split(",")]
@@ -179,8 +219,8 @@ def main():
 
     lib = N.lib()
     cid = CHAIN.encode()
-    chain = Chain(max(hs))
     ctx_lane, ctx_kb8, ctx_def = open_ctx(1 << 20), open_ctx(1), open_ctx(None)
+    chain = Chain(max(hs), ctx_def if args.real_keys else None)
 
     def many(ctx, a):
         rc = lib.cmtv_verify_commits_typed(ctx.handle, N.VERIFY_COMMIT, 0, cid, len(cid), a["n"], a["vs"], a["kt"],
@@ -258,7 +298,7 @@ def main():
         kq = np.percentile(kernel["lane"], [25, 75])
         scale = H / n_loop  # the loop's time for all H heights, had it run them
         print(json.dumps({
-            "tool": "bench_typed_commits", "heights": H, "validators": N_VALS, "signatures": n, "reps": rep,
+            "tool": "bench_typed_commits", "real_keys": args.real_keys, "heights": H, "validators": N_VALS, "signatures": n, "reps": rep,
             "msg_len": chain.msg_len, "loop_heights": n_loop,
             **{k + "_ms": round(v, 4) for k, v in med.items()},
             **{k + "_kernel_ms": round(v, 4) for k, v in kmed.items()},
