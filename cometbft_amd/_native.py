@@ -45,6 +45,12 @@ COMMIT_ERR_TRUST_LEVEL = 7
 COMMIT_PANIC_BAD_PUBKEY = 8
 COMMIT_PANIC_UNKNOWN_FLAG = 9
 
+# cmtv_merkle_proofs_verify: a proof's status, and what its leaf bytes are
+PROOF_OK, PROOF_ENEGTOTAL, PROOF_ENEGINDEX, PROOF_ELEAF, PROOF_EINDEX, PROOF_EEXTRA, PROOF_EMISSING, PROOF_EROOT = \
+    range(8)
+PROOF_LEAF_ITEM = 0
+PROOF_LEAF_TX = 1
+
 # every symbol include/cmtverify.h declares (checked by tests/test_abi.py)
 EXPORTS = (
     "cmtv_open", "cmtv_open_devices", "cmtv_device_count", "cmtv_device_ordinal", "cmtv_device_stream", "cmtv_sync",
@@ -62,6 +68,8 @@ EXPORTS = (
     "cmtv_merkle_root", "cmtv_merkle_roots", "cmtv_valset_hash", "cmtv_valset_hashes", "cmtv_commit_hash",
     "cmtv_commit_hashes", "cmtv_validator_bytes", "cmtv_commit_sig_bytes",
     "cmtv_txs_hash", "cmtv_txs_hashes", "cmtv_header_hash", "cmtv_header_hashes", "cmtv_header_leaf_bytes",
+    "cmtv_merkle_proof_len", "cmtv_merkle_proofs_len", "cmtv_merkle_proofs", "cmtv_txs_proofs",
+    "cmtv_part_set_proofs", "cmtv_merkle_proofs_verify",
 )
 
 
@@ -296,6 +304,20 @@ def lib() -> ctypes.CDLL:
     L.cmtv_header_hashes.restype = ctypes.c_int
     L.cmtv_header_leaf_bytes.argtypes = [ctypes.POINTER(cmtv_header), u32, _u8p, sz]
     L.cmtv_header_leaf_bytes.restype = i64
+    i64p = ctypes.POINTER(i64)
+    L.cmtv_merkle_proof_len.argtypes = [u64, u64]
+    L.cmtv_merkle_proof_len.restype = ctypes.c_int
+    L.cmtv_merkle_proofs_len.argtypes = [sz, u32p, ctypes.POINTER(u64)]
+    L.cmtv_merkle_proofs_len.restype = ctypes.c_int
+    L.cmtv_merkle_proofs.argtypes = [vp, sz, u32p, _u8p, u32p, _u8p, _u8p, u32p, _u8p, sz]
+    L.cmtv_merkle_proofs.restype = ctypes.c_int
+    L.cmtv_txs_proofs.argtypes = [vp, sz, u32p, _u8p, u32p, _u8p, _u8p, u32p, _u8p, sz]
+    L.cmtv_txs_proofs.restype = ctypes.c_int
+    L.cmtv_part_set_proofs.argtypes = [vp, _u8p, sz, u32, u32p, _u8p, _u8p, u32p, _u8p, sz]
+    L.cmtv_part_set_proofs.restype = ctypes.c_int
+    L.cmtv_merkle_proofs_verify.argtypes = [vp, sz, i64p, i64p, _u8p, u32p, _u8p, sz, _u8p, u32p, _u8p, u32p, u32,
+                                            _u8p, _u8p, ctypes.POINTER(ctypes.c_int)]
+    L.cmtv_merkle_proofs_verify.restype = ctypes.c_int
     _lib = L
     return L
 

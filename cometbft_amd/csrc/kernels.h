@@ -245,4 +245,19 @@ hipError_t launch_merkle_pass(MerkleLeafKind kind, const MerkleLeaves& leaves, c
 //   i32[k n + h]   nanos, LastBlockID's part-set total (k = 0, 1)
 hipError_t launch_header_hash(const MerkleLeaves& fields, uint32_t n, uint32_t* out, hipStream_t s);
 
+// Merkle inclusion proofs (merkle_proof.hip, merkle_proof.h). A proof pass is
+// launch_merkle_pass's (kMerkleItems, kMerkleTxs or kMerkleNodes) that also
+// writes each leaf's hash (leaf_hashes, 8 words a leaf; null after the first
+// pass) and, per leaf g of the pass, its aunts inside its block from node
+// aunt_off[g] of `aunts` on. The spreading launch appends the aunts of the
+// passes after the first to every leaf's proof; the verify launch is
+// Proof.Verify of n proofs, one lane each.
+struct ProofSpread;
+struct ProofBatch;
+hipError_t launch_merkle_proof_pass(MerkleLeafKind kind, const MerkleLeaves& leaves, const uint32_t* wg_off,
+                                    const uint32_t* leaf_off, uint32_t n_trees, uint32_t n_wg, uint32_t* out,
+                                    uint32_t* leaf_hashes, const uint32_t* aunt_off, uint32_t* aunts, hipStream_t s);
+hipError_t launch_merkle_proof_spread(const ProofSpread& S, hipStream_t s);
+hipError_t launch_merkle_proofs_verify(const ProofBatch& P, uint32_t n, hipStream_t s);
+
 }  // namespace cmtv

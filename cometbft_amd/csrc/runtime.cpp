@@ -172,7 +172,7 @@ static void release_device(CmtvDev& D) {
   for (HostBuf* b : {&D.h_in, &D.h_out, &D.h_zc, &D.h_tags, &D.h_zin}) b->release();
   D.d_tags = nullptr;  // h_tags' device pointer
   for (MerkleSlot& M : D.merkle) {
-    for (DevBuf* b : {&M.d_in, &M.d_nodes}) b->release();
+    for (DevBuf* b : {&M.d_in, &M.d_nodes, &M.d_out}) b->release();
     for (HostBuf* b : {&M.h_in, &M.h_out}) b->release();
     if (M.done) (void)hipEventDestroy(M.done);
     M.done = nullptr;

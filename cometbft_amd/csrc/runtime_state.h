@@ -332,10 +332,10 @@ struct BulkLane {
 // A staging slot of the merkle engine (merkle.cpp): a run's pinned staging
 // block and its copy on the device, the passes' nodes, the roots back, and
 // the event after them. Two per device: one run is packed while the other
-// is hashed.
+// is hashed. d_out: what a proof run writes besides its roots (merkle_proof.cpp).
 struct MerkleSlot {
   HostBuf h_in, h_out;
-  DevBuf d_in, d_nodes;
+  DevBuf d_in, d_nodes, d_out;
   hipEvent_t done = nullptr;
 };
 

@@ -470,6 +470,249 @@ def txs_hash(txs, ctx: Context | None = None) -> bytes:
     return bytes(out)
 
 
+# ---------------------------------------------------------------- merkle proofs
+MAX_AUNTS = 100  # crypto/merkle/proof.go MaxAunts
+HASH_SIZE = 32   # tmhash.Size
+
+
+def _p64(a):
+    return a.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))
+
+
+def _pack_items(items):
+    """(blob, offsets) of a list of byte strings, as the C calls take them."""
+    off = np.zeros(len(items) + 1, np.uint32)
+    if items:
+        off[1:] = np.cumsum([len(it) for it in items])
+    return np.frombuffer(b"".join(items) + b"\0\0\0\0", np.uint8).copy(), off
+
+
+def _proof_error(status: int, proof, root, out_hash: bytes):
+    """Proof.Verify's error string (proof.go:52-74) for a status of cmtv_merkle_proofs_verify."""
+    if status == N.PROOF_OK:
+        return None
+    if status == N.PROOF_ENEGTOTAL:
+        return "proof total must be positive"
+    if status == N.PROOF_ENEGINDEX:
+        return "proof index cannot be negative"
+    if status == N.PROOF_ELEAF:
+        return f"invalid leaf hash: wanted {out_hash.hex().upper()} got {proof.leaf_hash.hex().upper()}"
+    if status == N.PROOF_EINDEX:
+        return f"compute root hash: invalid index {proof.index} and/or total {proof.total}"
+    if status == N.PROOF_EEXTRA:
+        return "compute root hash: unexpected inner hashes"
+    if status == N.PROOF_EMISSING:
+        return "compute root hash: expected at least one inner hash"
+    return f"invalid root hash: wanted {root.hex().upper()} got {out_hash.hex().upper()}"
+
+
+def _verify_proofs_raw(proofs, roots, leaves, leaf_kind, root_idx, ctx):
+    """(status, out_hash) per proof from one cmtv_merkle_proofs_verify call.
+    Any number of aunts goes to the device (more than 63 cannot verify). A
+    leaf hash that is not 32 bytes cannot equal a computed one: with leaves the
+    device is given zeros in its place, which fail the same check, and the
+    error string quotes the proof's own. Where the reference would go on to
+    hash a leaf hash (no leaf check) or an aunt of another size as it is, this
+    raises ValueError with ValidateBasic's string instead."""
+    ctx = ctx or default_context()
+    n = len(proofs)
+    if n == 0:
+        return [], []
+    for p in proofs:
+        for i, a in enumerate(p.aunts):
+            if len(a) != HASH_SIZE:
+                raise ValueError(f"expected Aunts#{i} size to be {HASH_SIZE}, got {len(a)}")
+        if len(p.leaf_hash) != HASH_SIZE and leaves is None:
+            raise ValueError(f"expected LeafHash size to be {HASH_SIZE}, got {len(p.leaf_hash)}")
+    total = np.array([p.total for p in proofs], np.int64)
+    index = np.array([p.index for p in proofs], np.int64)
+    lh = np.frombuffer(b"".join(p.leaf_hash if len(p.leaf_hash) == HASH_SIZE else bytes(HASH_SIZE) for p in proofs),
+                       np.uint8).copy()
+    aunts, aunt_off = _pack_items([b"".join(p.aunts) for p in proofs])
+    aunt_off //= HASH_SIZE
+    rblob = _p8(np.frombuffer(b"".join(roots), np.uint8).copy()) if roots is not None else None
+    ridx = _p32(np.asarray(root_idx, np.uint32)) if root_idx is not None else None
+    if leaves is not None:
+        lblob, loff = _pack_items(list(leaves))
+        lblob, loff = _p8(lblob), _p32(loff)
+    else:
+        lblob, loff = None, None
+    status = (ctypes.c_uint8 * n)()
+    out = (ctypes.c_uint8 * (32 * n))()
+    N.check(N.lib().cmtv_merkle_proofs_verify(ctx.handle, n, _p64(total), _p64(index), _p8(lh), _p32(aunt_off),
+                                              _p8(aunts), len(roots) if roots is not None else 0, rblob, ridx, lblob,
+                                              loff, leaf_kind, status, out, None), "cmtv_merkle_proofs_verify")
+    return list(status), _roots(out, n)
+
+
+@dataclass
+class Proof:
+    """crypto/merkle/proof.go Proof: aunts run from the leaf's sibling up to a child of the root."""
+    total: int
+    index: int
+    leaf_hash: bytes
+    aunts: list = field(default_factory=list)
+
+    def validate_shape(self) -> Optional[str]:
+        """The size rules of ValidateBasic, which the device calls rely on."""
+        if len(self.leaf_hash) != HASH_SIZE:
+            return f"expected LeafHash size to be {HASH_SIZE}, got {len(self.leaf_hash)}"
+        if len(self.aunts) > MAX_AUNTS:
+            return f"expected no more than {MAX_AUNTS} aunts, got {len(self.aunts)}"
+        for i, a in enumerate(self.aunts):
+            if len(a) != HASH_SIZE:
+                return f"expected Aunts#{i} size to be {HASH_SIZE}, got {len(a)}"
+        return None
+
+    def validate_basic(self) -> None:
+        """ValidateBasic (proof.go:113), pure Python; raises ValueError."""
+        if self.total < 0:
+            raise ValueError("negative Total")
+        if self.index < 0:
+            raise ValueError("negative Index")
+        err = self.validate_shape()
+        if err is not None:
+            raise ValueError(err)
+
+    def verify(self, root, leaf: bytes, ctx: Context | None = None) -> None:
+        """Proof.Verify (proof.go:52) on the device; raises ValueError with the reference's string."""
+        if root is None:
+            raise ValueError("invalid root hash: cannot be nil")
+        err = verify_proofs([self], [bytes(root)], [leaf], ctx=ctx)[0]
+        if err is not None:
+            raise ValueError(err)
+
+    def compute_root_hash(self, ctx: Context | None = None) -> bytes:
+        """ComputeRootHash (proof.go:77); ReferencePanic where the reference panics."""
+        st, out = _verify_proofs_raw([self], None, None, N.PROOF_LEAF_ITEM, None, ctx)
+        if st[0] != N.PROOF_OK:
+            # (no leaf and no root is checked: the statuses left are those of computeHashFromAunts,
+            # after the two sign checks, which ComputeRootHash reports as an invalid index)
+            status = N.PROOF_EINDEX if st[0] in (N.PROOF_ENEGTOTAL, N.PROOF_ENEGINDEX) else st[0]
+            msg = _proof_error(status, self, b"", out[0])[len("compute root hash: "):]
+            raise ReferencePanic(f"ComputeRootHash errored {msg}")
+        return out[0]
+
+
+def verify_proofs(proofs, roots, leaves, leaf_kind: int = N.PROOF_LEAF_ITEM, root_idx=None,
+                  ctx: Context | None = None) -> list:
+    """Proof.Verify of every proof in one cmtv_merkle_proofs_verify call: None,
+    or the reference's error string. roots: one per proof, or any number with
+    root_idx naming each proof's. leaves: the leaf bytes per proof, or None for
+    no leaf check. A root that is not 32 bytes cannot match (Verify compares
+    the bytes): it is compared on the host. A leaf hash of another size and
+    more than 100 aunts get Verify's own strings ("invalid leaf hash ...",
+    "unexpected inner hashes"), not ValidateBasic's; an aunt of another size
+    raises ValueError with ValidateBasic's string (_verify_proofs_raw)."""
+    proofs = list(proofs)
+    roots = [bytes(r) for r in roots]
+    dev_roots = [r if len(r) == HASH_SIZE else bytes(HASH_SIZE) for r in roots]
+    st, out = _verify_proofs_raw(proofs, dev_roots, leaves, leaf_kind, root_idx, ctx)
+    errs = []
+    for i, p in enumerate(proofs):
+        root = roots[root_idx[i] if root_idx is not None else i]
+        status = st[i]
+        if status in (N.PROOF_OK, N.PROOF_EROOT):
+            status = N.PROOF_OK if out[i] == root else N.PROOF_EROOT
+        errs.append(_proof_error(status, p, root, out[i]))
+    return errs
+
+
+@dataclass
+class TxProof:
+    """types/tx.go:96 TxProof."""
+    root_hash: bytes
+    data: bytes
+    proof: Proof
+
+    def leaf(self) -> bytes:
+        return hashlib.sha256(self.data).digest()
+
+    def validate(self, data_hash: bytes, ctx: Context | None = None) -> None:
+        """TxProof.Validate (types/tx.go:109); raises ValueError with the reference's string."""
+        if bytes(data_hash) != bytes(self.root_hash):
+            raise ValueError("proof matches different data hash")
+        if self.proof.index < 0:
+            raise ValueError("proof index cannot be negative")
+        if self.proof.total <= 0:
+            raise ValueError("proof total must be positive")
+        if any(len(a) != HASH_SIZE for a in self.proof.aunts) or \
+                verify_proofs([self.proof], [self.root_hash], [self.data], N.PROOF_LEAF_TX, ctx=ctx)[0] is not None:
+            raise ValueError("proof is not internally consistent")
+
+
+def _proofs_call(fn, name, trees, ctx):
+    ctx = ctx or default_context()
+    trees = [list(t) for t in trees]
+    if not trees:
+        return []
+    items = [it for t in trees for it in t]
+    tree_off = np.zeros(len(trees) + 1, np.uint32)
+    tree_off[1:] = np.cumsum([len(t) for t in trees])
+    blob, item_off = _pack_items(items)
+    n_aunts = ctypes.c_uint64()
+    N.check(N.lib().cmtv_merkle_proofs_len(len(trees), _p32(tree_off), ctypes.byref(n_aunts)),
+            "cmtv_merkle_proofs_len")
+    roots = (ctypes.c_uint8 * (32 * len(trees)))()
+    lh = (ctypes.c_uint8 * (32 * max(len(items), 1)))()
+    aunt_off = np.zeros(len(items) + 1, np.uint32)
+    aunts = (ctypes.c_uint8 * (32 * max(n_aunts.value, 1)))()
+    N.check(fn(ctx.handle, len(trees), _p32(tree_off), _p8(blob), _p32(item_off), roots, lh, _p32(aunt_off), aunts,
+               n_aunts.value), name)
+    return _split_proofs(_roots(roots, len(trees)), [len(t) for t in trees], bytes(lh), aunt_off, bytes(aunts))
+
+
+def _split_proofs(roots, sizes, lh, aunt_off, aunts):
+    """[(root, [Proof])] per tree from a building call's flat outputs."""
+    out, g = [], 0
+    for root, n in zip(roots, sizes):
+        proofs = []
+        for i in range(n):
+            a, b = int(aunt_off[g]), int(aunt_off[g + 1])
+            proofs.append(Proof(n, i, lh[32 * g: 32 * g + 32], [aunts[32 * k: 32 * k + 32] for k in range(a, b)]))
+            g += 1
+        out.append((root, proofs))
+    return out
+
+
+def proofs_from_trees(trees, ctx: Context | None = None) -> list:
+    """ProofsFromByteSlices (proof.go:35) of every tree in one
+    cmtv_merkle_proofs call: [(root, [Proof])]."""
+    return _proofs_call(N.lib().cmtv_merkle_proofs, "cmtv_merkle_proofs", trees, ctx)
+
+
+def proofs_from_byte_slices(items, ctx: Context | None = None):
+    """ProofsFromByteSlices of one list of byte strings: (root, [Proof])."""
+    return proofs_from_trees([items], ctx)[0]
+
+
+def txs_proofs(txs, ctx: Context | None = None):
+    """Txs.Proof(i) (types/tx.go:80) for every i in one cmtv_txs_proofs call: (root, [TxProof])."""
+    txs = list(txs)
+    root, proofs = _proofs_call(N.lib().cmtv_txs_proofs, "cmtv_txs_proofs", [txs], ctx)[0]
+    return root, [TxProof(root, tx, p) for tx, p in zip(txs, proofs)]
+
+
+def part_set_from_data(data: bytes, part_size: int = 65536, ctx: Context | None = None):
+    """NewPartSetFromData (types/part_set.go:166) through cmtv_part_set_proofs:
+    (PartSetHeader, [Proof]), part i being data[i * part_size: (i + 1) * part_size]."""
+    ctx = ctx or default_context()
+    if part_size <= 0 or len(data) + part_size > 2**32:
+        raise ValueError("part_size must be positive and len(data) + part_size at most 2^32")
+    n = (len(data) + part_size - 1) // part_size
+    n_aunts = sum(N.lib().cmtv_merkle_proof_len(n, i) for i in range(n))
+    blob = np.frombuffer(bytes(data) + b"\0\0\0\0", np.uint8).copy()
+    total = ctypes.c_uint32()
+    root = (ctypes.c_uint8 * 32)()
+    lh = (ctypes.c_uint8 * (32 * max(n, 1)))()
+    aunt_off = np.zeros(n + 1, np.uint32)
+    aunts = (ctypes.c_uint8 * (32 * max(n_aunts, 1)))()
+    N.check(N.lib().cmtv_part_set_proofs(ctx.handle, _p8(blob), len(data), part_size, ctypes.byref(total), root, lh,
+                                         _p32(aunt_off), aunts, n_aunts), "cmtv_part_set_proofs")
+    (r, proofs), = _split_proofs([bytes(root)], [total.value], bytes(lh), aunt_off, bytes(aunts))
+    return PartSetHeader(total.value, r), proofs
+
+
 def _verify(vals: ValidatorSet, kind, chain_id, block_id, height, commit, num, den, ctx, mode):
     ctx = ctx or default_context()
     vs, keep_v = vals._pack()

@@ -780,6 +780,84 @@ int cmtv_header_hashes(cmtv_ctx* ctx, size_t n, const cmtv_header* hs, uint8_t* 
  * length, leaf 3 of a time that StdTimeMarshal refuses. */
 int64_t cmtv_header_leaf_bytes(const cmtv_header* h, uint32_t leaf, uint8_t* out, size_t cap);
 
+/* ------------------------------------------------------------ merkle proofs */
+
+/* Merkle inclusion proofs (crypto/merkle/proof.go): Proof{Total, Index,
+ * LeafHash, Aunts}, the aunts from the leaf's sibling up to a child of the
+ * root. Building computes every node of every tree once and keeps them; the
+ * rules of the merkle root calls above hold: blocking, thread-safe, the
+ * context's first device (CMTV_ENODEV once it is retired), argument errors
+ * before any device work, nothing written to any output unless the call
+ * returns CMTV_OK, a large call cut into runs internally (a run is bounded by
+ * its output bytes as well as its staged bytes). Replaces:
+ * types/part_set.go:166 NewPartSetFromData and :284 AddPart, types/tx.go:80
+ * Txs.Proof and :109 TxProof.Validate, types/results.go:28 ProveResult.
+ *
+ * cmtv_merkle_proof_len: the aunts of leaf index in a tree of total leaves,
+ * -1 when index >= total. cmtv_merkle_proofs_len: their sum over every leaf
+ * of every tree (tree_off as cmtv_merkle_roots; CMTV_EINVAL: a NULL pointer,
+ * decreasing offsets). Host only. */
+int cmtv_merkle_proof_len(uint64_t total, uint64_t index);
+int cmtv_merkle_proofs_len(size_t n_trees, const uint32_t* tree_off, uint64_t* n_aunts);
+
+/* ProofsFromByteSlices (proof.go:35) of n_trees trees: tree_off, items and
+ * item_off as cmtv_merkle_roots; n_items = tree_off[n_trees] - tree_off[0].
+ * roots n_trees x 32; leaf_hashes n_items x 32; aunt_off n_items + 1, written
+ * by the call: the aunts of item i (counted from tree_off[0]) are hashes
+ * aunt_off[i] .. aunt_off[i + 1] of aunts; aunts aunt_off[n_items] x 32 bytes,
+ * cap_aunts says how many hashes fit (CMTV_EINVAL when too few:
+ * cmtv_merkle_proofs_len tells). Item i's Total is its tree's item count, its
+ * Index its place in the tree. An empty tree has the root SHA-256("") and no
+ * proof. leaf_hashes, aunt_off and aunts may be NULL when there is no item.
+ * cmtv_txs_proofs: the same with a transaction in the place of an item
+ * (Txs.Proof, types/tx.go:80: leaf i is SHA-256(tx i)). */
+int cmtv_merkle_proofs(cmtv_ctx* ctx, size_t n_trees, const uint32_t* tree_off, const uint8_t* items,
+                       const uint32_t* item_off, uint8_t* roots, uint8_t* leaf_hashes, uint32_t* aunt_off,
+                       uint8_t* aunts, size_t cap_aunts);
+int cmtv_txs_proofs(cmtv_ctx* ctx, size_t n_blocks, const uint32_t* block_off, const uint8_t* txs,
+                    const uint32_t* tx_off, uint8_t* roots, uint8_t* leaf_hashes, uint32_t* aunt_off, uint8_t* aunts,
+                    size_t cap_aunts);
+/* NewPartSetFromData (types/part_set.go:166): *total = ceil(len / part_size)
+ * parts, part i = data[i part_size .. min((i + 1) part_size, len)), one tree
+ * over them; root 32 bytes, leaf_hashes *total x 32, aunt_off *total + 1,
+ * aunts and cap_aunts as above. CMTV_EINVAL: part_size 0, len + part_size >
+ * 2^32 (the reference's uint32 sum wraps), data NULL with len != 0. */
+int cmtv_part_set_proofs(cmtv_ctx* ctx, const uint8_t* data, size_t len, uint32_t part_size, uint32_t* total,
+                         uint8_t root[32], uint8_t* leaf_hashes, uint32_t* aunt_off, uint8_t* aunts,
+                         size_t cap_aunts);
+
+/* Proof.Verify (proof.go:52) of n proofs, one status byte each, in the
+ * reference's own order of checks. */
+enum {
+  CMTV_PROOF_OK = 0,        /* the proof verifies                                        */
+  CMTV_PROOF_ENEGTOTAL = 1, /* total < 0 (reported even when index is negative too)      */
+  CMTV_PROOF_ENEGINDEX = 2, /* index < 0                                                 */
+  CMTV_PROOF_ELEAF = 3,     /* leaf hash mismatch                                        */
+  CMTV_PROOF_EINDEX = 4,    /* "invalid index %d and/or total %d", total == 0 included   */
+  CMTV_PROOF_EEXTRA = 5,    /* "unexpected inner hashes"                                 */
+  CMTV_PROOF_EMISSING = 6,  /* "expected at least one inner hash"                        */
+  CMTV_PROOF_EROOT = 7      /* root mismatch                                             */
+};
+enum { CMTV_PROOF_LEAF_ITEM = 0, CMTV_PROOF_LEAF_TX = 1 };
+/* total, index: int64 x n; leaf_hashes n x 32; proof i's aunts are hashes
+ * aunt_off[i] .. aunt_off[i + 1] of aunts (n + 1 offsets, not decreasing; a
+ * count above 63 is a shape error, CMTV_PROOF_EEXTRA when no earlier check
+ * fails, and those aunts are never dereferenced: no int64 total has a proof
+ * that long). roots n_roots x 32 and root_idx n (each below n_roots; NULL:
+ * n_roots == n, proof i against root i); roots may be NULL when out_hash is
+ * not: no root check. leaves + leaf_off as items (both NULL: no leaf check,
+ * which is ComputeRootHash); leaf_kind CMTV_PROOF_LEAF_ITEM, or
+ * CMTV_PROOF_LEAF_TX: the leaf is SHA-256(leaf bytes), TxProof.Validate
+ * (types/tx.go:109). status n bytes; out_hash NULL or n x 32: the computed
+ * leaf hash on CMTV_PROOF_ELEAF, the computed root on CMTV_PROOF_OK and
+ * CMTV_PROOF_EROOT, zeros otherwise. *all_ok (may be NULL): 1 when every
+ * status is CMTV_PROOF_OK. */
+int cmtv_merkle_proofs_verify(cmtv_ctx* ctx, size_t n, const int64_t* total, const int64_t* index,
+                              const uint8_t* leaf_hashes, const uint32_t* aunt_off, const uint8_t* aunts,
+                              size_t n_roots, const uint8_t* roots, const uint32_t* root_idx, const uint8_t* leaves,
+                              const uint32_t* leaf_off, uint32_t leaf_kind, uint8_t* status, uint8_t* out_hash,
+                              int* all_ok);
+
 /* ------------------------------------------------------------ test-data generation */
 
 /* RFC 8032 key generation and deterministic signing on the device (the
