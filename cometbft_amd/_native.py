@@ -64,6 +64,7 @@ EXPORTS = (
     "cmtv_batch_new", "cmtv_batch_add", "cmtv_batch_len", "cmtv_batch_verify", "cmtv_batch_reset",
     "cmtv_batch_free", "cmtv_verify_commit", "cmtv_verify_commit_typed", "cmtv_verify_commits", "cmtv_verify_commits_typed", "cmtv_verdict_cache", "cmtv_keyset_cache", "cmtv_vote_sign_bytes", "cmtv_pubkeys_ed25519", "cmtv_sign_ed25519",
     "cmtv_privkey_secp256k1_from_secret", "cmtv_pubkeys_secp256k1", "cmtv_sign_secp256k1",
+    "cmtv_pubkeys_sr25519", "cmtv_sign_sr25519",
     "cmtv_alloc_pinned", "cmtv_free_pinned",
     "cmtv_merkle_root", "cmtv_merkle_roots", "cmtv_valset_hash", "cmtv_valset_hashes", "cmtv_commit_hash",
     "cmtv_commit_hashes", "cmtv_validator_bytes", "cmtv_commit_sig_bytes",
@@ -274,6 +275,10 @@ def lib() -> ctypes.CDLL:
     L.cmtv_pubkeys_secp256k1.restype = ctypes.c_int
     L.cmtv_sign_secp256k1.argtypes = [vp, sz, _u8p, sz, u32p, _u8p, u32p, _u8p]
     L.cmtv_sign_secp256k1.restype = ctypes.c_int
+    L.cmtv_pubkeys_sr25519.argtypes = [vp, sz, _u8p, _u8p, _u8p]
+    L.cmtv_pubkeys_sr25519.restype = ctypes.c_int
+    L.cmtv_sign_sr25519.argtypes = [vp, sz, _u8p, sz, u32p, _u8p, u32p, _u8p]
+    L.cmtv_sign_sr25519.restype = ctypes.c_int
     L.cmtv_alloc_pinned.argtypes = [vp, sz, ctypes.POINTER(vp)]
     L.cmtv_alloc_pinned.restype = ctypes.c_int
     L.cmtv_free_pinned.argtypes = [vp, vp]

@@ -401,6 +401,43 @@ class Context:
         N.check(rc, "cmtv_sign_secp256k1")
         return out[:n]
 
+    def pubkeys_sr25519(self, mini: np.ndarray, with_addresses: bool = False):
+        """The 32-byte ristretto255 keys of n 32-byte mini secrets
+        (PrivKey.PubKey, crypto/sr25519/privkey.go:46), made on the device;
+        with_addresses also their 20-byte addresses SHA-256(pk)[:20]
+        (PubKey.Address, pubkey.go:25). Test data only: variable time."""
+        mini = np.ascontiguousarray(mini, dtype=np.uint8).reshape(-1, 32)
+        n = mini.shape[0]
+        pk = np.zeros((max(n, 1), 32), np.uint8)
+        addr = np.zeros((max(n, 1), 20), np.uint8) if with_addresses else None
+        rc = N.lib().cmtv_pubkeys_sr25519(self._h, n, _u8(mini), _u8(pk), _u8(addr) if with_addresses else None)
+        N.check(rc, "cmtv_pubkeys_sr25519")
+        return (pk[:n], addr[:n]) if with_addresses else pk[:n]
+
+    def sign_sr25519(self, mini: np.ndarray, msg: np.ndarray, msg_off: np.ndarray, key_idx=None) -> np.ndarray:
+        """R || s signatures with the marker bit (PrivKey.Sign, privkey.go:25,
+        with the deterministic witness include/cmtverify.h states) made on the
+        device; signature i by mini[key_idx[i]] (None: by mini[i]) over
+        msg[msg_off[i]:msg_off[i + 1]]. Test data only."""
+        mini = np.ascontiguousarray(mini, dtype=np.uint8).reshape(-1, 32)
+        off = np.ascontiguousarray(msg_off, dtype=np.uint32)
+        n = len(off) - 1
+        msg = np.ascontiguousarray(msg, dtype=np.uint8)
+        if msg.size == 0:
+            msg = np.zeros(1, np.uint8)
+        out = np.zeros((max(n, 1), 64), np.uint8)
+        u32p = ctypes.POINTER(ctypes.c_uint32)
+        kp = None
+        if key_idx is not None:
+            key_idx = np.ascontiguousarray(key_idx, dtype=np.uint32)
+            if key_idx.shape[0] != n:
+                raise ValueError("key_idx / msg_off sizes disagree")
+            kp = key_idx.ctypes.data_as(u32p)
+        rc = N.lib().cmtv_sign_sr25519(self._h, mini.shape[0], _u8(mini), n, kp, _u8(msg), off.ctypes.data_as(u32p),
+                                       _u8(out))
+        N.check(rc, "cmtv_sign_sr25519")
+        return out[:n]
+
 
 class KeySet:
     """Registered public keys (cmtv_keyset): per-key combs resident in HBM."""

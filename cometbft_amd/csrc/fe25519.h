@@ -483,5 +483,12 @@ CMTV_HD void fe_const_sqrtm1(fe& h) {
 #pragma unroll
   for (int i = 0; i < 10; i++) h.v[i] = c[i];
 }
+// 1/sqrt(a - d), a = -1 (RFC 9496 4.1 INVSQRT_A_MINUS_D): ristretto255 ENCODE
+CMTV_HD void fe_const_invsqrt_amd(fe& h) {
+  const uint32_t c[10] = {0x05d40ea, 0x03f6aa0, 0x257d339, 0x0bad20b, 0x274bc58,
+                          0x001d840, 0x13dc8ff, 0x19442d8, 0x05cfaff, 0x1e1b224};
+#pragma unroll
+  for (int i = 0; i < 10; i++) h.v[i] = c[i];
+}
 
 }  // namespace cmtv

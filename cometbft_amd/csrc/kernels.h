@@ -202,6 +202,15 @@ hipError_t launch_secp_pubkey(uint32_t n, const void* priv, const uint32_t* gtab
 // signature i by key key_idx[i] (null: key i) over msg[off[i] .. off[i + 1]); out_sig n x 64 bytes (4-byte aligned)
 hipError_t launch_secp_sign(uint32_t n, const void* priv, const void* key_idx, const void* msg, const void* off,
                             const uint32_t* gtab, void* out_sig, hipStream_t s);
+// sr25519 test data (sr25519_sign.hip): mini n x 32 bytes (16-byte aligned);
+// btab the shared fixed-base table; out_pk n x 32 bytes, out_addr n x 20 bytes
+// (4-byte aligned) or null.
+hipError_t launch_pubkey_sr25519(uint32_t n, const void* mini, const uint32_t* btab, void* out_pk, void* out_addr,
+                                 hipStream_t s);
+// signature i by key key_idx[i] (null: key i) over msg[off[i] .. off[i + 1]); prog / nops the transcript's prefix
+// sponge (merlin.h sr_prefix_state); out_sig n x 64 bytes (4-byte aligned)
+hipError_t launch_sign_sr25519(uint32_t n, const void* mini, const void* key_idx, const void* msg, const void* off,
+                               const uint32_t* btab, const uint32_t* prog, int nops, void* out_sig, hipStream_t s);
 
 // One pass of the merkle engine (merkle.hip, merkle.h): n_wg workgroups, each
 // an aligned block of one tree's leaves reduced to node g of `out` (8 words a

@@ -432,4 +432,68 @@ int secp_sign_host_locked(cmtv_ctx* ctx, CmtvDev& D, size_t n_keys, const uint8_
   return CMTV_OK;
 }
 
+// ---------------------------------------------------------------- sr25519 test data
+// cmtv_pubkeys_sr25519 / cmtv_sign_sr25519 behind their argument checks
+// (runtime.cpp), in the shape of the secp256k1 pair above: the same staging
+// layout, the shared fixed-base table and the transcript's prefix sponge the
+// context holds since it was made.
+
+int sr_pubkeys_host_locked(cmtv_ctx* ctx, CmtvDev& D, size_t n, const uint8_t* mini, uint8_t* out_pk,
+                           uint8_t* out_addr) {
+  hipError_t e;
+  const size_t o_addr = align_up(32 * n, 256);
+  if ((e = D.d_in.ensure(32 * n)) != hipSuccess) return hip_fail(e);
+  if ((e = D.d_out.ensure(o_addr + (out_addr ? 20 * n : 0))) != hipSuccess) return hip_fail(e);
+  auto* dout = static_cast<uint8_t*>(D.d_out.p);
+  if ((e = hipMemcpyAsync(D.d_in.p, mini, 32 * n, hipMemcpyHostToDevice, D.stream)) != hipSuccess)
+    return hip_fail(e);
+  LaunchScope L{ctx, D, D.stream};
+  if ((e = L.begin()) != hipSuccess) return hip_fail(e);
+  for (size_t c = 0; c < n; c += kChunk) {
+    const uint32_t cn = (uint32_t)std::min<size_t>(kChunk, n - c);
+    e = launch_pubkey_sr25519(cn, static_cast<uint8_t*>(D.d_in.p) + 32 * c, D.d_btab, dout + 32 * c,
+                              out_addr ? dout + o_addr + 20 * c : nullptr, D.stream);
+    if ((e = L.launched(e)) != hipSuccess) return hip_fail(e);
+  }
+  if (const int rc = L.finish_uncounted()) return rc;
+  if ((e = hipMemcpyAsync(out_pk, dout, 32 * n, hipMemcpyDeviceToHost, D.stream)) != hipSuccess) return hip_fail(e);
+  if (out_addr &&
+      (e = hipMemcpyAsync(out_addr, dout + o_addr, 20 * n, hipMemcpyDeviceToHost, D.stream)) != hipSuccess)
+    return hip_fail(e);
+  if ((e = hipStreamSynchronize(D.stream)) != hipSuccess) return hip_fail(e);
+  return CMTV_OK;
+}
+
+int sr_sign_host_locked(cmtv_ctx* ctx, CmtvDev& D, size_t n_keys, const uint8_t* mini, size_t n,
+                        const uint32_t* key_idx, const uint8_t* msg, const uint32_t* msg_off, uint8_t* out_sig) {
+  hipError_t e;
+  const size_t msg_bytes = msg_off[n];
+  const size_t o_idx = align_up(32 * n_keys, 256), o_off = align_up(o_idx + (key_idx ? 4 * n : 0), 256);
+  const size_t o_msg = align_up(o_off + 4 * (n + 1), 256), in_bytes = align_up(o_msg + msg_bytes + 16, 256);
+  if ((e = D.h_in.ensure(in_bytes)) != hipSuccess) return hip_fail(e);
+  if ((e = D.d_in.ensure(in_bytes)) != hipSuccess) return hip_fail(e);
+  if ((e = D.d_out.ensure(64 * n)) != hipSuccess) return hip_fail(e);
+  auto* hin = static_cast<uint8_t*>(D.h_in.p);
+  std::memcpy(hin, mini, 32 * n_keys);
+  if (key_idx) std::memcpy(hin + o_idx, key_idx, 4 * n);
+  std::memcpy(hin + o_off, msg_off, 4 * (n + 1));
+  if (msg_bytes) std::memcpy(hin + o_msg, msg, msg_bytes);
+  auto* din = static_cast<uint8_t*>(D.d_in.p);
+  if ((e = hipMemcpyAsync(din, hin, in_bytes, hipMemcpyHostToDevice, D.stream)) != hipSuccess) return hip_fail(e);
+  LaunchScope L{ctx, D, D.stream};
+  if ((e = L.begin()) != hipSuccess) return hip_fail(e);
+  for (size_t c = 0; c < n; c += kChunk) {
+    const uint32_t cn = (uint32_t)std::min<size_t>(kChunk, n - c);
+    e = launch_sign_sr25519(cn, key_idx ? din : din + 32 * c, key_idx ? din + o_idx + 4 * c : nullptr, din + o_msg,
+                            din + o_off + 4 * c, D.d_btab, D.d_srprog, ctx->sr_nops,
+                            static_cast<uint8_t*>(D.d_out.p) + 64 * c, D.stream);
+    if ((e = L.launched(e)) != hipSuccess) return hip_fail(e);
+  }
+  if (const int rc = L.finish_uncounted()) return rc;
+  if ((e = hipMemcpyAsync(out_sig, D.d_out.p, 64 * n, hipMemcpyDeviceToHost, D.stream)) != hipSuccess)
+    return hip_fail(e);
+  if ((e = hipStreamSynchronize(D.stream)) != hipSuccess) return hip_fail(e);
+  return CMTV_OK;
+}
+
 }  // namespace cmtv

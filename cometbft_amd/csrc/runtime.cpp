@@ -833,7 +833,7 @@ int cmtv_privkey_secp256k1_from_secret(const uint8_t* secret, size_t len, uint8_
   return CMTV_OK;
 }
 
-// the device both secp256k1 test-data calls run on: the first live one, made current
+// the device the secp256k1 and sr25519 test-data calls run on: the first live one, made current
 static int secp_testdata_dev(cmtv_ctx* ctx, std::unique_lock<std::mutex>& lk, CmtvDev*& D) {
   if (ctx_lock(ctx, lk) != CMTV_OK) return CMTV_ENODEV;
   if (ctx->live.empty()) return CMTV_ENODEV;
@@ -867,6 +867,31 @@ int cmtv_sign_secp256k1(cmtv_ctx* ctx, size_t n_keys, const uint8_t* priv, size_
   CmtvDev* D = nullptr;
   if (const int rc = secp_testdata_dev(ctx, lk, D)) return rc;
   return secp_sign_host_locked(ctx, *D, n_keys, priv, n, key_idx, msg, msg_off, out_sig);
+}
+
+// every 32-byte string is a mini secret: no key-range check
+int cmtv_pubkeys_sr25519(cmtv_ctx* ctx, size_t n, const uint8_t* mini, uint8_t* out_pk, uint8_t* out_addr) {
+  if (!ctx || n > (1ull << 31)) return CMTV_EINVAL;
+  if (n == 0) return CMTV_OK;
+  if (!mini || !out_pk) return CMTV_EINVAL;
+  std::unique_lock<std::mutex> lk;
+  CmtvDev* D = nullptr;
+  if (const int rc = secp_testdata_dev(ctx, lk, D)) return rc;
+  return sr_pubkeys_host_locked(ctx, *D, n, mini, out_pk, out_addr);
+}
+
+int cmtv_sign_sr25519(cmtv_ctx* ctx, size_t n_keys, const uint8_t* mini, size_t n, const uint32_t* key_idx,
+                      const uint8_t* msg, const uint32_t* msg_off, uint8_t* out_sig) {
+  if (!ctx || n > (1ull << 31) || n_keys > (1ull << 31)) return CMTV_EINVAL;
+  if (!key_idx && n != n_keys) return CMTV_EINVAL;
+  if (n == 0) return CMTV_OK;
+  if (!mini || !msg_off || !out_sig || n_keys == 0 || (!msg && msg_off[n] != 0)) return CMTV_EINVAL;
+  for (size_t i = 0; i < n; i++)
+    if (msg_off[i + 1] < msg_off[i] || (key_idx && key_idx[i] >= n_keys)) return CMTV_EINVAL;
+  std::unique_lock<std::mutex> lk;
+  CmtvDev* D = nullptr;
+  if (const int rc = secp_testdata_dev(ctx, lk, D)) return rc;
+  return sr_sign_host_locked(ctx, *D, n_keys, mini, n, key_idx, msg, msg_off, out_sig);
 }
 
 }  // extern "C"

@@ -752,6 +752,11 @@ int secp_pubkeys_host_locked(cmtv_ctx* ctx, CmtvDev& D, size_t n, const uint8_t*
                              uint8_t* out_addr);
 int secp_sign_host_locked(cmtv_ctx* ctx, CmtvDev& D, size_t n_keys, const uint8_t* priv, size_t n,
                           const uint32_t* key_idx, const uint8_t* msg, const uint32_t* msg_off, uint8_t* out_sig);
+// the same for sr25519 (sr25519_sign.hip): mini secrets, any 32 bytes each
+int sr_pubkeys_host_locked(cmtv_ctx* ctx, CmtvDev& D, size_t n, const uint8_t* mini, uint8_t* out_pk,
+                           uint8_t* out_addr);
+int sr_sign_host_locked(cmtv_ctx* ctx, CmtvDev& D, size_t n_keys, const uint8_t* mini, size_t n,
+                        const uint32_t* key_idx, const uint8_t* msg, const uint32_t* msg_off, uint8_t* out_sig);
 
 // host_batch.cpp: a host batch straight to the devices (no verdict cache),
 // generic keys or (ks) registered ones; secp256k1 on devs[0]. Lock held.

@@ -296,4 +296,86 @@ CMTV_HD void sha512_prefixed(uint32_t out[16], const uint32_t pre[PW], const uin
   }
 }
 
+// The same with a prefix of PB bytes, any PB <= 64: pre holds ceil(PB / 4)
+// little-endian byte words, the bytes past PB in the last one zero. (A form
+// of its own: sha512_prefixed's callers are the verifiers' hot paths and keep
+// the code they were measured with.)
+//
+// With PR = PB % 4 the message byte at stream position pos sits PR bytes
+// later than in an aligned word, so the funnel shift is (sh - PR) mod 4 and,
+// when PR > sh, the stream word that holds the prefix's last bytes pairs the
+// aligned word "before" the message's first (index -1: never loaded, zero)
+// with that first word. The loads are sha512_prefixed's: only aligned words
+// holding a message byte.
+template <int PB>
+CMTV_HD void sha512_prefixed_bytes(uint32_t out[16], const uint32_t pre[(PB + 3) / 4], const uint8_t* msg,
+                                   uint32_t mlen) {
+  static_assert(PB > 0 && PB <= 64, "the prefix lies inside block 0");
+  constexpr uint32_t PR = PB % 4, PF = PB - PR;  // PF: the prefix's whole words, in bytes
+  uint64_t st[8] = {0x6a09e667f3bcc908ULL, 0xbb67ae8584caa73bULL, 0x3c6ef372fe94f82bULL,
+                    0xa54ff53a5f1d36f1ULL, 0x510e527fade682d1ULL, 0x9b05688c2b3e6c1fULL,
+                    0x1f83d9abfb41bd6bULL, 0x5be0cd19137e2179ULL};
+  const uint32_t total = PB + mlen;
+  const uint32_t nblocks = (total + 17 + 127) / 128;
+  const uint64_t bitlen = (uint64_t)total * 8;
+  const uint32_t sh = (uint32_t)((uintptr_t)msg & 3);
+  const uint32_t* mw = reinterpret_cast<const uint32_t*>(msg - sh);
+  const uint32_t nwords = (sh + mlen + 3) / 4;
+  const uint32_t jmax = nwords ? nwords - 1 : 0u;
+  const uint32_t* mb = nwords ? mw : &g_sha512_no_word;
+  const uint32_t fsh = (sh - PR) & 3;        // funnel shift
+  const int jlead = sh < PR ? -1 : 0;         // aligned word under stream position PF
+  auto tail_word = [&](uint32_t pos, uint32_t lo, uint32_t hi) -> uint32_t {
+    uint32_t v = funnel_bytes(hi, lo, fsh);
+    if (PR && pos == PF) v = (v & ~((1u << (8 * PR)) - 1u)) | pre[PF / 4];
+    const int r = (int)total - (int)pos;  // stream bytes left in this word
+    const uint32_t rr = r < 0 ? 0u : (r > 4 ? 4u : (uint32_t)r);
+    const uint32_t keep = (uint32_t)((1ull << (8 * rr)) - 1u);
+    const uint32_t pad = (r >= 0 && r < 4) ? (0x80u << (8 * rr)) : 0u;
+    return (v & keep) | pad;
+  };
+  auto be64 = [](uint32_t lo_word, uint32_t hi_word) -> uint64_t {
+    return ((uint64_t)__builtin_bswap32(lo_word) << 32) | __builtin_bswap32(hi_word);
+  };
+#pragma unroll 1
+  for (uint32_t b = 0; b < nblocks; b++) {
+    // mv[k] = aligned message word j0 + k: the stream word at block offset
+    // off is funnel(mv[off/4], mv[off/4 + 1]); indices outside the message
+    // (negative ones wrap to huge) load clamped and are zeroed
+    const int j0 = (int)(b * 32) - (int)(PF / 4) + jlead;
+    uint32_t mv[33];
+#pragma unroll
+    for (int k = 0; k < 33; k++) {
+      const uint32_t j = (uint32_t)(j0 + k);
+      mv[k] = mb[j < nwords ? j : jmax];
+    }
+#pragma unroll
+    for (int k = 0; k < 33; k++) mv[k] = (uint32_t)(j0 + k) < nwords ? mv[k] : 0u;
+    uint64_t w[16];
+#pragma unroll
+    for (int t = 0; t < 16; t++) {
+      uint32_t lw[2];
+#pragma unroll
+      for (int h = 0; h < 2; h++) {
+        const uint32_t off = 8 * t + 4 * h;
+        if (b == 0 && off < PF)
+          lw[h] = pre[off / 4];
+        else
+          lw[h] = tail_word(b * 128 + off, mv[off / 4], mv[off / 4 + 1]);
+      }
+      uint64_t word = be64(lw[0], lw[1]);
+      if (b == nblocks - 1 && t == 15) word = bitlen;
+      w[t] = word;
+    }
+    sha512_compress(st, w);
+  }
+#pragma unroll
+  for (int i = 0; i < 8; i++) {
+    const uint64_t v = st[i];
+    const uint32_t hi = (uint32_t)(v >> 32), lo = (uint32_t)v;
+    out[2 * i] = __builtin_bswap32(hi);
+    out[2 * i + 1] = __builtin_bswap32(lo);
+  }
+}
+
 }  // namespace cmtv

@@ -10,7 +10,10 @@ sign-bytes by the library's CanonicalVote encoder.
 secp256k1 and mixed sets (make_secp256k1_validator_set / make_secp256k1_commit)
 are made the same way: private keys GenPrivKeySecp256k1("cmtverify/val/secp256k1/" || i)
 (crypto/secp256k1/secp256k1.go:107), keys, addresses and RFC 6979 signatures
-from the device (cmtv_pubkeys_secp256k1 / cmtv_sign_secp256k1).
+from the device (cmtv_pubkeys_secp256k1 / cmtv_sign_secp256k1). sr25519 and
+three-way mixed sets (make_typed_validator_set / make_typed_commit) likewise:
+mini secrets SHA-256("cmtverify/val/sr25519/" || i), keys, addresses and
+signatures from cmtv_pubkeys_sr25519 / cmtv_sign_sr25519.
 
 Workload definition:
   seed_i  = SHA-256("cmtverify/val/" || i), voting power 10, set sorted by address
@@ -99,39 +102,55 @@ def secp256k1_validator_privkeys(n: int, offset: int = 0) -> np.ndarray:
                      for i in range(n)], dtype=np.uint8).reshape(n, 32)
 
 
+def sr25519_validator_minis(n: int, offset: int = 0) -> np.ndarray:
+    """mini_i = SHA-256("cmtverify/val/sr25519/" || i): any 32 bytes are a mini secret."""
+    return np.array([np.frombuffer(hashlib.sha256(b"cmtverify/val/sr25519/%d" % (offset + i)).digest(), np.uint8)
+                     for i in range(n)], dtype=np.uint8).reshape(n, 32)
+
+
 @dataclass
 class SyntheticTypedValidators:
-    secrets: np.ndarray   # n x 32, in validator-set order: a secp256k1 private key or an Ed25519 seed
-    key_types: list       # n of "secp256k1" / "ed25519"
+    # n x 32, in validator-set order: an Ed25519 seed, a secp256k1 private key or an sr25519 mini secret
+    secrets: np.ndarray
+    key_types: list       # n of "ed25519" / "secp256k1" / "sr25519"
     valset: ValidatorSet
 
 
-def make_secp256k1_validator_set(ctx: Context, n: int, power: int = 10, offset: int = 0,
-                                 n_ed25519: int = 0) -> SyntheticTypedValidators:
-    """n secp256k1 validators and, for a mixed set, n_ed25519 Ed25519 ones
-    (make_validator_set's seeds), sorted by address like NewValidatorSet."""
-    priv = secp256k1_validator_privkeys(n, offset)
-    pks, addrs = ctx.pubkeys_secp256k1(priv, with_addresses=True)
-    rows = [(bytes(a), bytes(pk), "secp256k1", priv[i]) for i, (pk, a) in enumerate(zip(pks, addrs))]
+def make_typed_validator_set(ctx: Context, n_ed25519: int = 0, n_secp256k1: int = 0, n_sr25519: int = 0,
+                             power: int = 10, offset: int = 0) -> SyntheticTypedValidators:
+    """A set of any mix of the three key types, every key and address from the
+    device, sorted by address like NewValidatorSet: make_validator_set's seeds,
+    secp256k1_validator_privkeys and sr25519_validator_minis, each from
+    `offset` on."""
+    rows = []
+    if n_secp256k1:
+        priv = secp256k1_validator_privkeys(n_secp256k1, offset)
+        pks, addrs = ctx.pubkeys_secp256k1(priv, with_addresses=True)
+        rows += [(bytes(a), bytes(pk), "secp256k1", priv[i]) for i, (pk, a) in enumerate(zip(pks, addrs))]
     if n_ed25519:
         seeds = validator_seeds(n_ed25519, offset)
         for pk, seed in zip(ctx.pubkeys(seeds), seeds):
             rows.append((hashlib.sha256(bytes(pk)).digest()[:20], bytes(pk), "ed25519", seed))
+    if n_sr25519:
+        minis = sr25519_validator_minis(n_sr25519, offset)
+        pks, addrs = ctx.pubkeys_sr25519(minis, with_addresses=True)
+        rows += [(bytes(a), bytes(pk), "sr25519", minis[i]) for i, (pk, a) in enumerate(zip(pks, addrs))]
     rows.sort(key=lambda r: r[0])
     vals = ValidatorSet([Validator(pk, power, key_type=kt) for _, pk, kt, _ in rows])
     secrets = np.array([r[3] for r in rows], np.uint8).reshape(len(rows), 32)
     return SyntheticTypedValidators(secrets, [r[2] for r in rows], vals)
 
 
-def make_secp256k1_commit(ctx: Context, sv: SyntheticTypedValidators, height: int, round_: int = 0,
-                          chain_id: str = CHAIN_ID, flags=None):
-    """make_commit for a set of make_secp256k1_validator_set: (Commit, msgs,
-    sig array), every present validator signing with its own key type."""
+def make_typed_commit(ctx: Context, sv: SyntheticTypedValidators, height: int, round_: int = 0,
+                      chain_id: str = CHAIN_ID, flags=None):
+    """make_commit for a set of make_typed_validator_set: (Commit, msgs, sig
+    array), every present validator signing with its own key type's device
+    signer."""
     n = len(sv.valset.validators)
     flags = [BLOCK_ID_FLAG_COMMIT] * n if flags is None else list(flags)
     msgs = commit_messages(n, height, round_, chain_id, flags)
     sigs = np.zeros((n, 64), np.uint8)
-    for kt, sign in (("secp256k1", ctx.sign_secp256k1), ("ed25519", ctx.sign)):
+    for kt, sign in (("secp256k1", ctx.sign_secp256k1), ("ed25519", ctx.sign), ("sr25519", ctx.sign_sr25519)):
         idx = np.array([i for i in range(n) if sv.key_types[i] == kt], np.uint32)
         if idx.size:
             m, off = pack_messages([msgs[i] for i in idx])
@@ -144,6 +163,19 @@ def make_secp256k1_commit(ctx: Context, sv: SyntheticTypedValidators, height: in
         else:
             css.append(CommitSig(flags[i], sv.valset.validators[i].address, timestamp(height, i), bytes(sigs[i])))
     return Commit(height, round_, bid, css), msgs, sigs
+
+
+def make_secp256k1_validator_set(ctx: Context, n: int, power: int = 10, offset: int = 0,
+                                 n_ed25519: int = 0) -> SyntheticTypedValidators:
+    """n secp256k1 validators and, for a mixed set, n_ed25519 Ed25519 ones
+    (make_validator_set's seeds), sorted by address like NewValidatorSet."""
+    return make_typed_validator_set(ctx, n_ed25519=n_ed25519, n_secp256k1=n, power=power, offset=offset)
+
+
+def make_secp256k1_commit(ctx: Context, sv: SyntheticTypedValidators, height: int, round_: int = 0,
+                          chain_id: str = CHAIN_ID, flags=None):
+    """make_typed_commit under its first name."""
+    return make_typed_commit(ctx, sv, height, round_, chain_id, flags)
 
 
 _TEMPLATE_HEIGHT = 1000

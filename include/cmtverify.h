@@ -900,6 +900,50 @@ int cmtv_sign_secp256k1(cmtv_ctx* ctx, size_t n_keys, const uint8_t* priv /* n_k
                         const uint32_t* key_idx /* n, or NULL */, const uint8_t* msg,
                         const uint32_t* msg_off /* n + 1 */, uint8_t* out_sig /* n x 64 */);
 
+/* The same for sr25519 (the reference's PrivKey.PubKey, PubKey.Address and
+ * PrivKey.Sign, crypto/sr25519/privkey.go:46,25 and pubkey.go:25).
+ *
+ * NOT A SIGNER FOR KEYS THAT MATTER, as above: the kernels are variable-time
+ * (table lookups by secret digits), and the private keys are copied into the
+ * HBM of a device other processes may share. These calls make synthetic
+ * validator sets and commits for tests and benchmarks; they are no privval.
+ *
+ * A private key is the 32-byte mini secret, as PrivKey.Sign and PrivKey.PubKey
+ * treat it (NewMiniSecretKeyFromRaw -> ExpandEd25519); every 32-byte string is
+ * one, so there is no key-range error. With h = SHA-512(mini):
+ *   key   = clamp(h[0:32]) >> 3, clamp being h[0] &= 248, h[31] &= 63,
+ *           h[31] |= 64: a value in [2^251, 2^252), below L as it stands
+ *   nonce = h[32:64]
+ * cmtv_pubkeys_sr25519: the 32-byte keys ristretto255_encode([key]B) (RFC 9496
+ * 4.3.2) and, when out_addr is not NULL, the addresses SHA-256(key)[:20].
+ * cmtv_sign_sr25519: R || s with sig[63] |= 0x80, where
+ *   r = SHA-512("cmtverify/sr25519-witness" || nonce || msg) mod L
+ *       (the label is 25 bytes)
+ *   R = ristretto255_encode([r]B)
+ *   k = the merlin challenge of NewSigningContext([]byte{}, msg) over the
+ *       public key and R, exactly what the verifier computes, mod L
+ *   s = k key + r mod L
+ * The witness r is this library's own deterministic choice (the one the
+ * test oracle's sign() defines). go-schnorrkel draws r from a transcript RNG
+ * seeded with OS randomness, so no Go signature's bytes can be reproduced, and
+ * any r yields a signature the reference accepts. GenPrivKeyFromSecret
+ * (privkey.go:103) has no form here: it returns go-schnorrkel's encoding of
+ * the expanded key, which is not in the tree to pin; callers derive mini
+ * secrets themselves.
+ * Signature i is by mini[key_idx[i]] over msg[msg_off[i] .. msg_off[i + 1]);
+ * key_idx NULL: n == n_keys and signature i is by key i.
+ *
+ * Both calls are blocking, take and fill host buffers and run on the
+ * context's first live device, one launch per 262,144 items. CMTV_EINVAL,
+ * checked before any device work and with nothing written: a NULL context, a
+ * NULL required pointer, n > 2^31, a decreasing msg_off, a key_idx[i] >=
+ * n_keys, key_idx NULL with n != n_keys. n == 0 is CMTV_OK. */
+int cmtv_pubkeys_sr25519(cmtv_ctx* ctx, size_t n, const uint8_t* mini /* n x 32 */, uint8_t* out_pk /* n x 32 */,
+                         uint8_t* out_addr /* n x 20, or NULL */);
+int cmtv_sign_sr25519(cmtv_ctx* ctx, size_t n_keys, const uint8_t* mini /* n_keys x 32 */, size_t n,
+                      const uint32_t* key_idx /* n, or NULL */, const uint8_t* msg,
+                      const uint32_t* msg_off /* n + 1 */, uint8_t* out_sig /* n x 64 */);
+
 #ifdef __cplusplus
 }
 #endif
